@@ -8,11 +8,14 @@ ray_steps = B*L*H*W*N nominal, never "steps executed".
     forward-only normals + shadow + shade.  One "step" = one pass of the hot path over one batch: one
     gcfr_render_from_depth_fwd enqueue -- what RelightNet.forward runs for T8:353-522 -- (prepass: depth repack, statistics,
     depth bounds, light prep; then the ray march with the normals stencil and the shading fused into its epilogue), inputs
-    resident in HBM.  The same line carries, measured in the same run: `normals_in_*` (SURVEY 8d's accounting form, normals
-    as an input: rounds 1-3's headline step), `config5_*` (configs[4]'s per-GPU shape: 1 face x 18 lights x 512x512 x 320),
-    `train_*` (configs[2]: batch 32, the full training step) and `worst_case`.  Steps are independent batches: `--streams S` (default 4) keeps S of them in
-    flight on S HIP streams, each a hipGraph replay of a preallocated RenderFwdPlan -- `value` is that throughput;
-    `single_stream` in the same line is the one-batch-at-a-time rate (= the batch-8 latency).
+    resident in HBM.  Steps are independent batches: `--streams S` (default 4) keeps S of them in flight on S HIP streams,
+    each a hipGraph replay of a preallocated RenderFwdPlan -- `value` is that throughput.  A plain run sets up, warms up,
+    times exactly `--steps` steps in one fenced region and prints the line (`--dump-outputs DIR` also writes what the last
+    step returned).  With `--full` the same line also carries, measured in the same run: the parity spot check against the
+    C oracle, `single_stream` (the one-batch-at-a-time rate = the batch-8 latency), `normals_in_*` (SURVEY 8d's
+    accounting form, normals as an input: rounds 1-3's headline step), `config5_*` (configs[4]'s per-GPU shape: 1 face x
+    18 lights x 512x512 x 320), `train_*` (configs[2]: batch 32, the full training step), `relight_e2e_*`, `worst_case`,
+    and the roofline and CPU baselines below.
 --workload train (BASELINE configs[2]; configs[3] under torchrun): batch of 32 faces per GPU, one full training step
     (RelightNet forward incl. the fused render block, PatchGAN every 5th step, seven losses, backward through the
     fused backward kernel, two Adam steps; DistributedDataParallel over RCCL when WORLD_SIZE > 1).
@@ -21,7 +24,7 @@ Multi-GPU (`python -m torch.distributed.run --nproc-per-node N bench.py --gpus N
 rank works on its own batch with no data-path collective ("weak" scaling; training adds DDP's gradient all-reduce);
 the timed region is bracketed by barrier + synchronize on both sides and the max over ranks is reported.
 
-The JSON line also carries
+With --full the JSON line also carries
   roofline     -- for the dominant kernel, measured live with HIP events on the launch stream (un-captured plan calls
                   on one stream, library-recorded events around the kernel):
                   bound "valu": the SIMD issue time the kernel's instruction mix needs (rocprofv3 SQ_INSTS_VALU_* per
@@ -432,6 +435,7 @@ class RenderRig:
                 self.graph_error, self.use_graph = repr(e), False
                 torch.cuda.synchronize()
         self.streams = rig_streams(dev, self.n_streams)
+        self.eager_out = None
 
     # -- data ----------------------------------------------------------------------------------
     def _device_batch(self, j):
@@ -510,7 +514,15 @@ class RenderRig:
             elif self.use_plans:
                 self.plans[b](*self.inputs[b])
             else:
-                self.eager_step(self.base_opt)
+                self.eager_out = self.eager_step(self.base_opt)
+
+    def step_outputs(self, i, n_streams=None):
+        """what step i of a round-robin over `n_streams` streams handed its caller: the result dict of the plan it ran on (the
+        next step on that plan overwrites it) or of the eager call (the last one issued).  Read after a fence."""
+        if not self.use_plans:
+            return self.eager_out
+        n_streams = n_streams or self.n_streams
+        return self.plans[i % n_streams if self.n_batches == self.n_streams else i % self.n_batches].out
 
     def timed(self, n_steps, n_streams=None):
         """n_steps steps round-robin over the first `n_streams` streams, fenced on both sides -> (seconds: max over
@@ -775,6 +787,70 @@ def library_srchash():
         return None
 
 
+DUMP_LIMIT_BYTES = 64 * 2 ** 20
+
+
+def dump_outputs(outputs, out_dir, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs DIR: every tensor of `outputs` (what the timed path handed its caller in its last step) as DIR/<name>.npy --
+    f64 outputs and 32/64-bit integers (argmin) as float64, everything else as float32.  When the arrays hold more than `limit`
+    bytes in all, each is replaced by the same share of its flattened values at a seeded choice of indices (sorted; the same
+    indices for the same shapes, so that two builds compare element for element).  Returns {name: shape written}."""
+    arrays = {}
+    for name, t in outputs.items():
+        if not torch.is_tensor(t):
+            continue
+        x = t.detach().cpu().numpy()
+        wide = x.dtype == np.float64 or (x.dtype.kind in "iu" and x.dtype.itemsize >= 4)
+        arrays[name] = x.astype(np.float64 if wide else np.float32)
+    total = sum(x.nbytes for x in arrays.values())
+    os.makedirs(out_dir, exist_ok=True)
+    written = {}
+    for name, x in sorted(arrays.items()):
+        if total > limit:
+            k = max(1, int(x.size * limit / total))
+            idx = np.sort(np.random.default_rng(0).choice(x.size, size=k, replace=False))
+            x = x.reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + ".npy"), x)
+        written[name] = list(x.shape)
+    return written
+
+
+def headline_line(a, rig, B, knobs, headline, from_depth, desc, value, elapsed, regions, per_rank_s, host_issue, layout):
+    """The keys of the render line that the headline region alone gives (a plain run prints these; --full adds its legs)."""
+    world, n_streams, rsps = rig.rk.world, rig.n_streams, rig.ray_steps_per_step
+    return {
+        "metric": "ray_steps_per_sec", "value": value, "unit": "ray-steps/s", **{k: layout[k] for k in ("n_gpus", "rccl_ranks")},
+        "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * elapsed / a.steps,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64+f32",
+        "data": "synthetic" if a.data != "ffhq" else "ffhq-fixtures (3 checkpoint-derived faces tiled)",
+        # (advisor r04: `value` of rounds 1-3 timed gcfr_render_fwd with the normals handed in -- today's `normals_in_*`; since round 4
+        #  the step includes the normals stage, so `value` is not comparable across that boundary by itself)
+        "step_definition": ("gcfr_render_from_depth_fwd (normals stage inside the step; rounds 1-3: gcfr_render_fwd = normals_in_*)"
+                            if from_depth else "gcfr_render_fwd (normals handed in)"),
+        "config": {"workload": ("BASELINE configs[1]: " + desc) if headline else
+                               ("non-headline: batch=%d %s %dx%d faces per GPU, %d light(s) each, %d march steps, mask=%s, "
+                                "depth noise %g, knobs %s, %s%sforward-only shadow+shade; %d batch(es) in flight"
+                                % (B, a.data, a.size, a.size, a.lights, a.samples, a.mask, a.depth_noise, knobs or "default",
+                                   "argmin variant, " if a.argmin else "", "normals from depth, " if from_depth else "normals as input, ",
+                                   n_streams)),
+                   "faces_per_gpu": B, "H": a.size, "W": a.size, "lights_per_face": a.lights, "n_samples": a.samples,
+                   "parallelism": "dp%d" % world, "hip_streams": n_streams, "batches_in_flight": n_streams,
+                   "distinct_face_batches": n_streams,
+                   "host_path": ("RenderFwdPlan, hipGraph replay" if rig.use_graph else "RenderFwdPlan (preallocated outputs)")
+                   if rig.use_plans else "render_fwd (eager)"},
+        "process_layout": layout,
+        "per_rank": [{"rank": r, "seconds": s, "ray_steps_per_sec": rsps * a.steps / s} for r, s in enumerate(per_rank_s)],
+        "regions": regions,
+        "faces_per_sec": world * B * a.lights * a.steps / elapsed,
+        "host_issue_ms_per_step": 1e3 * host_issue / a.steps,
+        "ray_steps_per_sec_per_gpu": value / world,
+        # `value` is a throughput with `hip_streams` batches in flight (faces_in_flight below), not the rate of one batch
+        # of `faces_per_gpu` on its own -- that one is `single_stream` of --full (VERDICT r01 asked for both to be named)
+        "faces_in_flight_per_gpu": B * n_streams,
+        "throughput_in_flight": {"faces_in_flight_per_gpu": B * n_streams, "ray_steps_per_sec": value},
+    }
+
+
 def run_render(a, rk):
     knobs = {k: int(v) for k, v in (kv.split("=") for kv in a.tune.split(",") if kv)}
     B = a.faces
@@ -800,22 +876,40 @@ def run_render(a, rk):
         now = time.perf_counter()
         legs[name] = now - t_leg
         t_leg = now
-    # in-run parity spot check: the timed binary is checked in the run that times it
+    # in-run parity spot check (--full): the timed binary is checked in the run that times it
     spot = None
-    if rig.use_plans and not a.no_parity_check and not a.argmin and a.pixels == "all":
+    if a.full and rig.use_plans and not a.no_parity_check and not a.argmin and a.pixels == "all":
         spot = parity_spot_check(rig)
     for i in range(a.warmup):
         rig.issue(i, n_streams)
     elapsed, regions, own_elapsed, host_issue = rig.timed_regions(a.steps)
+    dumped = dump_outputs(rig.step_outputs(a.steps - 1), a.dump_outputs) if a.dump_outputs and rank == 0 else None
     per_rank_s = rk.gather(own_elapsed)
+    rsps = rig.ray_steps_per_step
+    value = world * rsps * a.steps / elapsed
+    desc = ("batch=%d %s 256x256 faces per GPU, 1 light each, 160 march steps, forward-only normals+shadow+shade "
+            "(gcfr_render_from_depth_fwd: what RelightNet.forward runs for T8:353-522); %d batch(es) in flight"
+            % (B, "synthetic" if a.data == "synthetic" else "FFHQ-fixture", n_streams))
+    if not a.full:
+        layout = rk.describe()                                                # (a collective: every rank calls it)
+        leg("headline_s")
+        if rank != 0:
+            return None
+        out = headline_line(a, rig, B, knobs, headline, from_depth, desc, value, elapsed, regions, per_rank_s, host_issue, layout)
+        out["config"]["parity_spot_check"] = "skipped (plain run: --full checks the timed plan against the C oracle)"
+        if rig.graph_error:
+            out["config"]["graph_capture_failed"] = rig.graph_error
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
+        legs["total_s"] = time.perf_counter() - T_START
+        out["run_seconds"] = legs
+        return out
     shadow_ms, shadow_ms_min, shadow_ms_max = rig.kernel_launch_ms(ev)
     single_steps = max(50, min(a.steps, 1000))
     if n_streams > 1:
         single_elapsed, single_regions, _, _ = rig.timed_regions(single_steps, 1)
     else:
         single_elapsed, single_regions = elapsed * single_steps / a.steps, regions
-    rsps = rig.ray_steps_per_step
-    value = world * rsps * a.steps / elapsed
     single = {"ms_per_step": 1e3 * single_elapsed / single_steps,
               "ray_steps_per_sec": world * rsps * single_steps / single_elapsed, "regions": single_regions,
               "note": "the same steps one at a time on ONE stream (hipGraph replay): the latency of one batch"}
@@ -1011,47 +1105,18 @@ def run_render(a, rk):
     else:       # no PMC mix for this workload / kernel selection: HBM accounting only
         roof = dict(hbm_line, kernel="shadow_fwd_quad_kernel" if mode != "direct" else "shadow_fwd_kernel",
                     avg_launch_ms=shadow_ms, traffic=None, kernel_ray_steps_per_sec=rsps / (shadow_ms * 1e-3))
-    desc = ("batch=%d %s 256x256 faces per GPU, 1 light each, 160 march steps, forward-only normals+shadow+shade "
-            "(gcfr_render_from_depth_fwd: what RelightNet.forward runs for T8:353-522); %d batch(es) in flight"
-            % (B, "synthetic" if a.data == "synthetic" else "FFHQ-fixture", n_streams))
-    out = {
-        "metric": "ray_steps_per_sec", "value": value, "unit": "ray-steps/s", **{k: layout[k] for k in ("n_gpus", "rccl_ranks")},
-        "steps": a.steps, "warmup": a.warmup, "ms_per_step": 1e3 * elapsed / a.steps,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f64+f32",
-        "data": "synthetic" if a.data != "ffhq" else "ffhq-fixtures (3 checkpoint-derived faces tiled)",
-        # (advisor r04: `value` of rounds 1-3 timed gcfr_render_fwd with the normals handed in -- today's `normals_in_*`; since round 4
-        #  the step includes the normals stage, so `value` is not comparable across that boundary by itself)
-        "step_definition": ("gcfr_render_from_depth_fwd (normals stage inside the step; rounds 1-3: gcfr_render_fwd = normals_in_*)"
-                            if from_depth else "gcfr_render_fwd (normals handed in)"),
-        "config": {"workload": ("BASELINE configs[1]: " + desc) if headline else
-                               ("non-headline: batch=%d %s %dx%d faces per GPU, %d light(s) each, %d march steps, mask=%s, "
-                                "depth noise %g, knobs %s, %s%sforward-only shadow+shade; %d batch(es) in flight"
-                                % (B, a.data, a.size, a.size, a.lights, a.samples, a.mask, a.depth_noise, knobs or "default",
-                                   "argmin variant, " if a.argmin else "", "normals from depth, " if from_depth else "normals as input, ",
-                                   n_streams)),
-                   "faces_per_gpu": B, "H": a.size, "W": a.size, "lights_per_face": a.lights, "n_samples": a.samples,
-                   "parallelism": "dp%d" % world, "hip_streams": n_streams, "batches_in_flight": n_streams,
-                   "distinct_face_batches": n_streams,
-                   "host_path": ("RenderFwdPlan, hipGraph replay" if rig.use_graph else "RenderFwdPlan (preallocated outputs)")
-                   if rig.use_plans else "render_fwd (eager)"},
-        "process_layout": layout,
-        "per_rank": [{"rank": r, "seconds": s, "ray_steps_per_sec": rsps * a.steps / s} for r, s in enumerate(per_rank_s)],
-        "regions": regions,
-        "faces_per_sec": world * B * a.lights * a.steps / elapsed,
-        "host_issue_ms_per_step": 1e3 * host_issue / a.steps,
-        "ray_steps_per_sec_per_gpu": value / world,
+    out = headline_line(a, rig, B, knobs, headline, from_depth, desc, value, elapsed, regions, per_rank_s, host_issue, layout)
+    out.update({
         "single_stream": single,
         "latency_one_batch_ms": single["ms_per_step"],
         # ... and with the prepass issued earlier on a side stream (gcfr_options.phase; RelightNet.forward does, under the albedo decoder)
         "latency_one_batch_prepass_hoisted_ms": single.get("march_only_ms_per_step"),
         "latency_one_batch_prepass_hoisted_note": "the march launch alone: its prepass was issued earlier and is OUTSIDE this time "
                                                   "(what a caller sees who hides it under other work); the full step is latency_one_batch_ms",
-        # `value` is a throughput with `hip_streams` batches in flight (faces_in_flight below), not the rate of one batch
-        # of `faces_per_gpu` on its own -- that one is `single_stream` (VERDICT r01 asked for both to be named)
-        "faces_in_flight_per_gpu": B * n_streams,
-        "throughput_in_flight": {"faces_in_flight_per_gpu": B * n_streams, "ray_steps_per_sec": value},
         "roofline": roof,
-    }
+    })
+    if dumped is not None:
+        out["dumped_outputs"] = dumped
     if relight_ranks is not None:
         out["relight_e2e"] = relight_ranks
         if "graph_faces_per_sec_1_light" in relight_ranks:
@@ -1302,9 +1367,9 @@ def run_dry(a, rk):
             "lights_per_face": a.lights, "face_lights_per_rank": faces * a.lights, "lights_split_across_ranks": False,
             "size": a.size, "samples": a.samples,
             # the end-to-end relight leg (relight_e2e_leg) belongs to rank 0's single-GPU headline line only
-            "relight_e2e_leg_runs": bool(rk.world == 1 and a.workload == "render" and not a.no_worst_case),
+            "relight_e2e_leg_runs": bool(a.full and rk.world == 1 and a.workload == "render" and not a.no_worst_case),
             # ... and with N > 1 ranks of the headline shape every rank relights its own photographs (relight_e2e_ranks, weak scaling)
-            "relight_e2e_ranks_runs": bool(rk.world > 1 and a.workload == "render" and not a.no_worst_case and a.size == 256
+            "relight_e2e_ranks_runs": bool(a.full and rk.world > 1 and a.workload == "render" and not a.no_worst_case and a.size == 256
                                            and a.lights == 1 and a.samples == 160 and a.faces == FACES_PER_GPU)}
 
 
@@ -1320,13 +1385,20 @@ def main():
     ap.add_argument("--data", choices=["synthetic", "ffhq", "train_depth"], default="synthetic",
                     help="ffhq = the three checkpoint-derived FFHQ fixture faces (tests/golden/inputs.npz) tiled to the batch; "
                          "train_depth = depth / light / albedo of a freshly initialised RelightNet (use with --from-depth --argmin)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--no-parity-check", action="store_true",
-                    help="skip the in-run parity spot check (face 0 of the timed batch through the timed plan vs the C oracle)")
-    ap.add_argument("--no-worst-case", action="store_true", help="skip the secondary workloads of the headline line")
+                    help="with --full: skip the in-run parity spot check (face 0 of the timed batch through the timed plan vs the C oracle)")
+    ap.add_argument("--no-worst-case", action="store_true", help="with --full: skip the secondary workloads of the headline line")
     ap.add_argument("--regions", type=int, default=0,
-                    help="number of fenced timed regions of `steps` steps (0 = auto: repeated when a region is shorter than 200 ms; "
-                         "profiling scripts pass 1)")
+                    help="number of fenced timed regions of `steps` steps (0 = one region; with --full: repeated when a region is "
+                         "shorter than 200 ms; profiling scripts pass 1)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline figure: the parity spot check, single-stream and march-only latency, "
+                         "kernel launch times and roofline, the secondary workloads, the training and end-to-end relight legs, "
+                         "the CPU baselines.  Without it a run sets up, warms up, times `steps` steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one handed its caller as DIR/<name>.npy (float32 / float64, "
+                         "at most 64 MB in all: a seeded sample of each array beyond that).  Render workload only")
     ap.add_argument("--oversubscribe", action="store_true",
                     help="allow more ranks than GPUs (ranks share GPUs, collectives over gloo): rehearses the launch path")
     ap.add_argument("--dry-run", action="store_true", help="rendezvous + one collective + JSON only (runs without a GPU)")
@@ -1343,7 +1415,7 @@ def main():
                          "fused into the march epilogue (three launches per step, the same bits); 'auto' = the product's rule: by "
                          "the number of lights per face (block.normals_stage_for: fused below 16)")
     ap.add_argument("--verbose-json", action="store_true", help="print the line with every note / sample description (default: compact)")
-    ap.add_argument("--no-train-leg", action="store_true", help="skip the configs[2] training-step leg of the headline line")
+    ap.add_argument("--no-train-leg", action="store_true", help="with --full: skip the configs[2] training-step leg of the headline line")
     ap.add_argument("--pixels", choices=["all", "mask"], default="all",
                     help="mask = RenderParams(pixels='mask') / gcfr_options.pixels = 1: pixels outside the mask are not marched (opt-in "
                          "deviation, include/gcfr.h; every loss of the training script multiplies them by the mask).  Non-headline.")
@@ -1374,12 +1446,16 @@ def main():
                     help="A/B: comma list of gcfr_options knobs, e.g. tile_w=32,ksplit=1,depth_bound_skip=0,group=2 "
                          "(never changes a result bit)")
     a = ap.parse_args()
+    if a.dump_outputs and a.workload != "render":
+        ap.error("--dump-outputs: the render workload only")
     if a.steps is None:
         a.steps = 3000 if a.workload == "render" else 20
     if a.warmup is None:
         a.warmup = 50 if a.workload == "render" else 6
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     global FORCED_REGIONS
-    FORCED_REGIONS = max(0, a.regions)
+    FORCED_REGIONS = max(0, a.regions) or (0 if a.full else 1)     # a plain run times exactly `steps` steps, once
     if a.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(self_launch(a))                     # this process becomes the launcher of N ranks
     rk = Ranks(a)

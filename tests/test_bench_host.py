@@ -23,6 +23,27 @@ def test_short_regions_are_repeated_and_long_ones_are_not():
         bench.FORCED_REGIONS = 0
 
 
+def test_dump_outputs_keeps_the_values_and_samples_the_same_indices_beyond_the_limit(tmp_path):
+    """--dump-outputs: f32 outputs stay f32, f64 and int32 (argmin) become f64, what is not a tensor is skipped; beyond the byte
+    limit every array keeps the same share of its values at seeded, sorted indices -- the same ones on every call."""
+    import torch
+    out = {"w": torch.rand(2, 3, 4), "fs": torch.rand(5, dtype=torch.float64), "argmin": torch.arange(6, dtype=torch.int32),
+           "mask": torch.ones(4, dtype=torch.uint8), "argmin_off": None, "n": 3}
+    assert bench.dump_outputs(out, str(tmp_path / "a")) == {"argmin": [6], "fs": [5], "mask": [4], "w": [2, 3, 4]}
+    load = lambda d, k: np.load(tmp_path / d / (k + ".npy"))
+    assert load("a", "w").dtype == np.float32 and np.array_equal(load("a", "w"), out["w"].numpy())
+    assert load("a", "fs").dtype == np.float64 and np.array_equal(load("a", "fs"), out["fs"].numpy())
+    assert load("a", "argmin").dtype == np.float64 and load("a", "argmin").tolist() == list(range(6))
+    assert load("a", "mask").dtype == np.float32
+    big = {"x": torch.arange(4096, dtype=torch.float32), "y": torch.arange(1024, dtype=torch.float64)}   # 24 KiB in all
+    for d in ("b", "c"):
+        bench.dump_outputs(big, str(tmp_path / d), limit=4096)
+    x, y = load("b", "x"), load("b", "y")
+    assert x.nbytes + y.nbytes <= 4096 and x.size == 682 and y.size == 170
+    assert np.array_equal(x, load("c", "x")) and np.array_equal(y, load("c", "y"))
+    assert (np.diff(x) > 0).all() and x[-1] < 4096                     # distinct indices in order (the values ARE the indices)
+
+
 def test_ffhq_fixture_workload_is_the_three_faces_tiled_and_mirrored():
     depth, mask, albedo, normals, light, amb = bench.ffhq_faces(8, first=0)
     inp = np.load(os.path.join(ROOT, "tests", "golden", "inputs.npz"))

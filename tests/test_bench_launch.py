@@ -9,6 +9,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -37,7 +38,7 @@ def test_gpus8_dry_run_keeps_the_books_of_configs3(workload):
     """BASELINE configs[3] (batch 256 over 8 GPUs) cannot run here; its BOOK-KEEPING can: eight self-launched ranks over gloo,
     every rank joins the collective, per-rank seeds rank * 10^6 + index, 32 faces per rank in the training workload (8 in the render
     workload), and the nominal ray-step accounting of one step x 8."""
-    p = _run(["--gpus", "8", "--dry-run", "--workload", workload], timeout=600)
+    p = _run(["--gpus", "8", "--dry-run", "--full", "--workload", workload], timeout=600)
     assert p.returncode == 0, p.stderr[-2000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout
@@ -69,11 +70,15 @@ def test_gpus8_dry_run_at_configs4_shape_keeps_every_light_of_a_face_on_one_rank
 
 
 def test_single_rank_needs_no_launcher():
-    p = _run(["--dry-run"])
+    p = _run(["--dry-run", "--full"])
     assert p.returncode == 0, p.stderr[-2000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])
     assert d["n_gpus"] == 1 and d["rccl_ranks"] == 1 and d["self_launched"] is False
     assert d["relight_e2e_leg_runs"] is True and d["lights_per_face"] == 1
+    # a plain run is the headline only: no side legs
+    p = _run(["--dry-run"])
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][0])["relight_e2e_leg_runs"] is False
 
 
 def test_without_a_gpu_the_real_command_fails_loudly():
@@ -106,3 +111,34 @@ def test_two_self_launched_ranks_run_the_real_workload_on_this_box(workload, ext
     assert len(d["per_rank"]) == 2 and all(r["seconds"] > 0 for r in d["per_rank"])
     assert d["rccl_ranks"] == (2 if n_dev >= 2 else None)
     assert d["value"] > 0 and d["config"]["parallelism"] == "dp2"
+
+
+@pytest.mark.gpu
+def test_plain_run_times_its_steps_once_and_dumps_the_last_steps_outputs(tmp_path):
+    """`bench.py --steps N --warmup W` is the headline alone: ONE fenced region of exactly N steps, no side legs.
+    --dump-outputs writes the result dict of the plan the last step ran on: with 7 steps on the default four streams that is
+    batch 2 (seed 16), whose face-0 minimum distance is the C oracle's bit for bit."""
+    p = _run(["--steps", "7", "--warmup", "2", "--dump-outputs", str(tmp_path)], timeout=600)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert {"metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"} <= set(d)
+    assert d["steps"] == 7 and d["regions"]["n"] == 1 and d["ms_per_step"] > 0
+    assert not {"roofline", "single_stream", "worst_case", "aux", "cpu_baseline"} & set(d)
+    rgb = np.load(tmp_path / "rendered_images.npy")
+    assert rgb.dtype == np.float32 and rgb.shape == (8, 1, 3, 256, 256) and np.isfinite(rgb).all()
+    assert d["dumped_outputs"]["rendered_images"] == [8, 1, 3, 256, 256]
+    sys.path.insert(0, os.path.join(ROOT, "oracle"))
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import c_oracle
+    from scenes import synth_faces
+    from geomconsistentfr_amd import RenderParams
+    prm = RenderParams()
+    depth, mask, _, _, light, _ = synth_faces(8, seed0=2 * 8, light_seed0=0)
+    _, pt = c_oracle.light_prep(light[:1].reshape(-1, 3), clamp_z_min=0.0)
+    md_ref, _ = c_oracle.shadow_min_distance(depth[:1], (mask[:1] != 0).astype(np.uint8), pt.reshape(1, 1, 3),
+                                             c_oracle.sample_table(prm.t0, prm.dt, prm.n_samples))
+    md = np.load(tmp_path / "minimum_distance.npy")
+    assert md.shape == (8, 1, 256, 256)
+    np.testing.assert_array_equal(md[:1].reshape(md_ref.shape), md_ref)

@@ -14,7 +14,7 @@ for round in 1 2 3; do
     elif [ "$cfg" = "default" ]; then extra="";
     elif [[ "$cfg" == lib:* ]]; then rest="${cfg#lib:}"; export GCFR_HIP_LIB="$REPO/geomconsistentfr_amd/lib/${rest%%:*}"; extra=""; [[ "$rest" == *:* ]] && extra="--tune ${rest#*:}";
     else extra="--tune $cfg"; fi
-    python bench.py $AB_EXTRA --no-cpu-baseline --steps ${AB_STEPS:-300} $extra 2>/dev/null | tail -1 | python -c "
+    python bench.py --full $AB_EXTRA --no-cpu-baseline --steps ${AB_STEPS:-300} $extra 2>/dev/null | tail -1 | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); s=d.get('single_stream') or {}; print('$cfg'.ljust(34), 'step %.1f G/s' % (d['value']/1e9), ' march %.4f ms' % (d['roofline']['avg_launch_ms']), ' 1-stream %.1f G/s' % (s.get('ray_steps_per_sec',0)/1e9))"
   done
 done

@@ -4,7 +4,7 @@
 REPO=${GRAFT_REPO_ROOT:-/root/repo}
 cd $REPO
 run() {
-  python bench.py --no-cpu-baseline "$@" 2>/dev/null | tail -1 | python -c "
+  python bench.py --full --no-cpu-baseline "$@" 2>/dev/null | tail -1 | python -c "
 import json,sys; d=json.loads(sys.stdin.read()); c=d['config']
 print('B=%-3d %dx%d L=%-2d N=%-3d %-55s step %.3f ms  %.1f G ray-steps/s  %.0f faces/s  | march %.3f ms %.1f G/s' % (c['faces_per_gpu'], c['H'], c['W'], c['lights_per_face'], c['n_samples'], ' '.join(sys.argv[1:]), d['ms_per_step'], d['value']/1e9, d['faces_per_sec'], d['roofline']['avg_launch_ms'], d['roofline']['kernel_ray_steps_per_sec']/1e9))" "$@"
 }
