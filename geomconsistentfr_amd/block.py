@@ -207,8 +207,11 @@ class Prepared:
 def source_signature(*tensors):
     """What identifies the CALLER's depth / mask / light between a prepass and its march: storage address, in-place version
     counter (shared by every view of a tensor, bumped by every in-place write), shape, strides and dtype of the tensors AS THE
-    CALLER HANDED THEM OVER -- before any f32 / u8 / contiguous conversion, whose copies have fresh addresses every time."""
-    return tuple((t.data_ptr(), t._version, tuple(t.shape), tuple(t.stride()), t.dtype) for t in tensors)
+    CALLER HANDED THEM OVER -- before any f32 / u8 / contiguous conversion, whose copies have fresh addresses every time.
+    Inference tensors (made under torch.inference_mode()) have no version counter: their entry carries None there, so the check
+    is WEAKER for them -- an in-place write to one inside inference mode between the prepass and its march goes unseen."""
+    return tuple((t.data_ptr(), None if t.is_inference() else t._version, tuple(t.shape), tuple(t.stride()), t.dtype)
+                 for t in tensors)
 
 
 def _prepass_key(shapes, params, options):
@@ -718,7 +721,9 @@ def camera_scalars(camera_matrix: torch.Tensor):
     pays it once).  A DEVICE tensor has to be copied back -- a device-to-host sync -- so its scalars are cached per tensor OBJECT: the entry holds a weak reference and the tensor's in-place version counter, and is
     only trusted while that very object is alive and unmodified (an address- or id-keyed cache would hand a freed
     tensor's scalars to whatever is allocated in its place).  Callers that keep one K on the device (Trainer does)
-    therefore synchronise once; callers that upload a fresh K every step should pass the host tensor instead."""
+    therefore synchronise once; callers that upload a fresh K every step should pass the host tensor instead.
+    An inference tensor (torch.inference_mode()) has no version counter to guard a cache entry: it is read every time and never
+    cached."""
     import weakref
 
     def read(K):
@@ -726,6 +731,8 @@ def camera_scalars(camera_matrix: torch.Tensor):
         same = K.shape[0] == 1 or bool((K == K[:1]).all())
         return (float(K[0, 0, 0]), float(K[0, 1, 1]), float(K[0, 0, 2]), float(K[0, 1, 2])) if same else None
 
+    if camera_matrix.is_inference():
+        return read(camera_matrix)
     key = id(camera_matrix)
     ent = _CAMERA_CACHE.get(key)
     if ent is not None and ent[0]() is camera_matrix and ent[1] == camera_matrix._version:

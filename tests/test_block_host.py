@@ -77,3 +77,32 @@ def test_camera_scalars_cache_follows_the_tensor_object_and_its_version():
     del K, two
     gc.collect()
     assert len(R._CAMERA_CACHE) == n0
+
+
+def test_source_signature_and_camera_scalars_take_inference_tensors():
+    """Tensors made under torch.inference_mode() have no version counter (reading `_version` raises): the signature records
+    None in its place -- a weaker check, stated in its docstring -- and camera_scalars reads such a matrix every time and never
+    caches it, so an in-place write is still seen.  A normal tensor handed over inside inference mode keeps its counter."""
+    from geomconsistentfr_amd import block as R
+    n0 = len(R._CAMERA_CACHE)
+    d_normal = torch.rand(2, 1, 8, 8)
+    with torch.inference_mode():
+        d, m, l = torch.rand(2, 1, 8, 8), torch.ones(2, 8, 8), torch.rand(2, 3)
+        s0 = R.source_signature(d, m, l)
+        assert s0 == R.source_signature(d, m, l) and [e[1] for e in s0] == [None] * 3
+        assert s0 != R.source_signature(d.clone(), m, l)
+        assert s0 != R.source_signature(d.reshape(2, 8, 8), m, l)
+        assert R.source_signature(d_normal, m, l)[0][1] == d_normal._version
+        K = torch.zeros(1, 3, 3, dtype=torch.float64)
+        K[:, 0, 0] = K[:, 1, 1] = 1570.0
+        K[:, 2, 2] = 1.0
+        K[:, 0, 2], K[:, 1, 2] = 128.0, 120.0
+        assert K.is_inference()
+        assert R.camera_scalars(K) == (1570.0, 1570.0, 128.0, 120.0)
+        assert len(R._CAMERA_CACHE) == n0                                            # not cached
+        K[:, 0, 0] = 700.0
+        assert R.camera_scalars(K) == (700.0, 1570.0, 128.0, 120.0)
+        two = torch.cat([K, K])
+        two[1, 0, 0] = 900.0
+        assert R.camera_scalars(two) is None
+    assert R.camera_scalars(K)[0] == 700.0 and len(R._CAMERA_CACHE) == n0             # outside inference mode too

@@ -323,3 +323,34 @@ def test_forward_lights_at_the_normals_stage_crossover(L):
             for k in (2, 4, 5, 6, 8):
                 assert torch.equal(many[k][:, l], one[k]), (k, l)
             assert torch.equal(many[9], one[9])
+
+
+def test_inference_mode_gives_the_no_grad_bytes():
+    """RelightNet.forward (eval, prepass hoisted), RelightNetSingleImage.forward_lights and inference.relight_images under
+    torch.inference_mode() give the bytes they give under torch.no_grad().  Every tensor made inside inference mode -- the head
+    outputs the prepass signs (block.source_signature), the host camera matrix (block.camera_scalars) -- has no version counter."""
+    from geomconsistentfr_amd import inference as inf
+    from geomconsistentfr_amd.relightnet import RelightNet, RelightNetSingleImage
+    B = 3
+    heads = _fixed_heads(B, 21)
+    train_form, single = _fixed(RelightNet, heads), _fixed(RelightNetSingleImage, heads)
+    assert train_form.hoist_prepass and single.hoist_prepass
+    images = np.random.default_rng(6).random((B, H, W, 3), dtype=np.float32)
+    lights = _lights11()[:4]
+
+    def run():
+        img = torch.from_numpy(images).to(DEV)
+        masks = torch.from_numpy(heads[3].astype(np.float64) / 255.0).reshape(1, H, W, 1).expand(B, -1, -1, -1).contiguous().to(DEV)
+        K = inf.camera_matrix(1570.0, H, W)                                  # a host tensor made in the mode under test
+        out = list(train_form(img, 200, K, masks))
+        out += list(single.forward_lights(img, 200, K, masks[0], lights))
+        out.append(torch.from_numpy(inf.relight_images(single, images, heads[3], np.repeat(lights[:1], B, 0), device=DEV)))
+        return [o.cpu() for o in out]
+
+    with torch.no_grad():
+        want = run()
+    with torch.inference_mode():
+        got = run()
+    assert len(got) == len(want) == 19
+    for i, (a, b) in enumerate(zip(got, want)):
+        assert torch.equal(a, b), i

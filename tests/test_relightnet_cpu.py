@@ -93,3 +93,85 @@ def test_reference_checkpoint_loads_and_network_outputs_match_the_reference():
     assert float((albedo - out[0]).abs().max()) <= 1e-5
     assert float((depth - out[1]).abs().max()) <= 1e-3          # depth is x100
     assert float((SL[:, :, :, 0] - out[11]).abs().max()) <= 1e-5
+
+
+class _Stop(Exception):
+    pass
+
+
+def _reference_heads(ref, x, epoch):
+    """albedo, depth and SL_lin2 of the reference's RelightNet.forward (T8:196-350), stopped where its render block would begin:
+    the two heads through forward hooks (then sigmoid and x100, as T8:290 / T8:350), SL_lin2 through one on linear_SL2."""
+    got = {}
+
+    def keep(key, stop=False):
+        def hook(_m, _inp, out):
+            got[key] = out.clone()
+            if stop:
+                raise _Stop()
+        return hook
+
+    hooks = [ref.linear_SL2.register_forward_hook(keep("SL")), ref.conv_albedo_c2_o.register_forward_hook(keep("albedo")),
+             ref.conv_depth_c2_o.register_forward_hook(keep("depth", stop=True))]
+    try:
+        with pytest.raises(_Stop):
+            ref(x, epoch, None, None)
+    finally:
+        for h in hooks:
+            h.remove()
+    return torch.sigmoid(got["albedo"]), 100.0 * got["depth"], got["SL"]
+
+
+def _assert_buffers_equal(a, b):
+    ba, bb = dict(a.named_buffers()), dict(b.named_buffers())
+    assert set(ba) == set(bb)
+    for k in ba:
+        assert torch.equal(ba[k], bb[k]), k
+
+
+@needs_ref
+def test_training_network_is_bit_equal_to_the_reference_at_every_skip_gate():
+    """RelightNet("3x3") holding T8.RelightNet's own state_dict (strict=True): albedo, depth and the lighting head's SL_lin2 are
+    the reference's bits in train() (batch-statistic BatchNorm) and eval() at epochs 0, 9, 11, 13, 15, 200 -- each side of every
+    skip gate (T8:245/258/271/283) --, and the BatchNorm running buffers the train-mode passes leave are equal too."""
+    import ref_shim
+    from geomconsistentfr_amd.relightnet import RelightNet
+    T8 = ref_shim.load("T8")
+    torch.manual_seed(0)
+    ref = T8.RelightNet()
+    mine = RelightNet("3x3")
+    mine.load_state_dict(ref.state_dict(), strict=True)
+    x = torch.rand(3, 256, 256, 3, generator=torch.Generator().manual_seed(1))
+    for train in (True, False):
+        ref.train(train)
+        mine.train(train)
+        for epoch in (0, 9, 11, 13, 15, 200):
+            with torch.no_grad():
+                want = _reference_heads(ref, x, epoch)
+                got = mine.features(x, epoch)
+            for name, a, b in zip(("albedo", "depth", "SL_lin2"), got, want):
+                assert torch.equal(a, b), (train, epoch, name, float((a - b).abs().max()))
+        if train:
+            _assert_buffers_equal(ref, mine)
+
+
+@needs_ref
+def test_patchgan_is_bit_equal_to_the_reference():
+    """PatchGAN holding T8.PatchGAN's state_dict (T8:15-35): the same logits in train() and eval(), the same running buffers."""
+    import ref_shim
+    from geomconsistentfr_amd.relightnet import PatchGAN
+    T8 = ref_shim.load("T8")
+    torch.manual_seed(0)
+    ref = T8.PatchGAN()
+    mine = PatchGAN()
+    mine.load_state_dict(ref.state_dict(), strict=True)
+    g = torch.Generator().manual_seed(2)
+    imgs = [torch.rand(3, 3, 256, 256, generator=g) for _ in range(2)]
+    for train in (True, False):
+        ref.train(train)
+        mine.train(train)
+        for x in imgs:
+            with torch.no_grad():
+                assert torch.equal(mine(x), ref(x)), train
+        if train:
+            _assert_buffers_equal(ref, mine)
