@@ -1,0 +1,108 @@
+"""The training step's image-loss head as one fused HIP forward and one fused HIP backward (csrc/gcfr_losses.hip).
+
+`image_losses(rendered, images, masks_fill)` computes what `train.generator_losses` and `Trainer.step` compute from
+`rendered_images` with a chain of ATen launches (T8:619, 633, 641, 643):
+
+    composite    = rendered * m + (1 - m) * images            bit-equal to the torch expression
+    recon_sq_sum = sum (rendered * m - images * m)^2           over (B,3,H,W)
+    mask_sum     = sum m                                       over (B,3,H,W): the mask counted once per channel
+    ssim         = the per-(image, channel) mean of the Gaussian-window SSIM map of (composite, images), before the relu
+
+The scalar arithmetic on top stays in torch, in `generator_losses`' own formulas, so corner cases behave as there (an all-zero
+mask gives 0 / 0):  recon = 20 * recon_sq_sum / mask_sum;  DSSIM = 8 * (1 - relu(ssim).mean(1).mean()) / 2.
+The gradient is with respect to `rendered` only.  There is no CPU path.
+"""
+import ctypes
+
+import torch
+
+from . import _lib
+
+WIN_SIZE, WIN_SIGMA = 11, 1.5          # pytorch_msssim.ssim's defaults, as T8:643 calls it
+_LAYOUTS = {"nhwc": 0, "nchw": 1}      # include/gcfr.h GCFR_IMAGES_NHWC / GCFR_IMAGES_NCHW
+
+
+_WINDOW = None
+
+
+def _window():
+    """the 11 f32 weights `train._gauss_window` produces, as a host array (made once: it is a constant)"""
+    global _WINDOW
+    if _WINDOW is None:
+        from .train import _gauss_window
+        g = _gauss_window(WIN_SIZE, WIN_SIGMA, "cpu", torch.float32)
+        _WINDOW = (ctypes.c_float * WIN_SIZE)(*g.tolist())
+    return _WINDOW
+
+
+class _ImageLossesFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, rendered, images, mask, layout, data_range):
+        L_ = _lib.load()
+        B, _, H, W = rendered.shape
+        dev = rendered.device
+        composite = torch.empty_like(rendered)
+        ssim = torch.empty((B, 3), dtype=torch.float32, device=dev)
+        sums = torch.empty(2, dtype=torch.float64, device=dev)
+        ws_bytes = int(L_.gcfr_image_losses_workspace_bytes(B, H, W))
+        ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=dev)
+        win = _window()
+        with torch.cuda.device(dev):
+            _lib.check(L_.gcfr_image_losses_fwd(rendered.data_ptr(), images.data_ptr(), mask.data_ptr() if mask is not None else None,
+                                                layout, B, H, W, ctypes.cast(win, ctypes.c_void_p), data_range, composite.data_ptr(),
+                                                ssim.data_ptr(), sums.data_ptr(), ws.data_ptr(), ws_bytes,
+                                                torch.cuda.current_stream(dev).cuda_stream), "gcfr_image_losses_fwd")
+        recon_sq_sum, mask_sum = sums[0].float(), sums[1].float()
+        ctx.save_for_backward(rendered, images, mask)
+        ctx.layout, ctx.data_range = layout, data_range
+        ctx.set_materialize_grads(False)          # an unused output's gradient arrives as None -> NULL, not as a tensor of zeros
+        ctx.mark_non_differentiable(mask_sum)
+        return composite, recon_sq_sum, mask_sum, ssim
+
+    @staticmethod
+    def backward(ctx, g_composite, g_recon, _g_mask_sum, g_ssim):
+        rendered, images, mask = ctx.saved_tensors
+        L_ = _lib.load()
+        B, _, H, W = rendered.shape
+        dev = rendered.device
+        f32c = lambda t: None if t is None else t.to(torch.float32).contiguous()
+        g_composite, g_recon, g_ssim = f32c(g_composite), f32c(g_recon), f32c(g_ssim)
+        ptr = lambda t: t.data_ptr() if t is not None else None
+        grad = torch.empty_like(rendered)
+        win = _window()
+        with torch.cuda.device(dev):
+            _lib.check(L_.gcfr_image_losses_bwd(rendered.data_ptr(), images.data_ptr(), ptr(mask), ctx.layout, B, H, W,
+                                                ctypes.cast(win, ctypes.c_void_p), ctx.data_range, ptr(g_composite), ptr(g_ssim),
+                                                ptr(g_recon), grad.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
+                       "gcfr_image_losses_bwd")
+        return grad, None, None, None, None
+
+
+def image_losses(rendered: torch.Tensor, images: torch.Tensor, masks_fill: torch.Tensor = None, *, images_layout: str = "nhwc",
+                 data_range: float = 1.0):
+    """(composite (B,3,H,W), recon_sq_sum (), mask_sum (), ssim (B,3)) of `rendered` (B,3,H,W) against the photograph `images`
+    ((B,H,W,3) for images_layout="nhwc", as batch["images"] holds it, or (B,3,H,W) for "nchw") under `masks_fill` (B,H,W),
+    (B,H,W,1) or (B,1,H,W), any values; None = no mask (composite = rendered, m = 1).  All f32 on one ROCm device.
+    `composite` and `ssim` are differentiable with respect to `rendered`, as is `recon_sq_sum`; `images` and `masks_fill` must not
+    require grad."""
+    if images_layout not in _LAYOUTS:
+        raise ValueError("images_layout must be 'nhwc' or 'nchw', got %r" % (images_layout,))
+    tensors = [t for t in (rendered, images, masks_fill) if t is not None]
+    if not all(t.is_cuda for t in tensors):
+        raise _lib.GcfrError("geomconsistentfr_amd has no CPU path: tensors must be on a ROCm device")
+    if any(t.dtype != torch.float32 or t.device != rendered.device for t in tensors):
+        raise _lib.GcfrError("image_losses: f32 tensors on one device")
+    if images.requires_grad or (masks_fill is not None and masks_fill.requires_grad):
+        raise _lib.GcfrError("image_losses differentiates with respect to `rendered` only: images / masks_fill must not require grad")
+    if rendered.dim() != 4 or rendered.shape[1] != 3:
+        raise _lib.GcfrError("rendered must be (B,3,H,W); got %s" % (tuple(rendered.shape),))
+    B, _, H, W = rendered.shape
+    want = (B, H, W, 3) if images_layout == "nhwc" else (B, 3, H, W)
+    if tuple(images.shape) != want:
+        raise _lib.GcfrError("images must be %s for images_layout=%r; got %s" % (want, images_layout, tuple(images.shape)))
+    if masks_fill is not None:
+        if masks_fill.numel() != B * H * W or tuple(masks_fill.shape) not in ((B, H, W), (B, H, W, 1), (B, 1, H, W)):
+            raise _lib.GcfrError("masks_fill must be (B,H,W), (B,H,W,1) or (B,1,H,W); got %s" % (tuple(masks_fill.shape),))
+        masks_fill = masks_fill.contiguous().reshape(B, H, W)
+    return _ImageLossesFunction.apply(rendered.contiguous(), images.contiguous(), masks_fill, _LAYOUTS[images_layout],
+                                      float(data_range))

@@ -3,8 +3,9 @@
 Mirrors the reference's step (train_raytracing_relighting_CelebAHQ_DSSIM_8x.py:582-656): PatchGAN
 discriminator step every GD_ratio iterations, then the generator step with seven losses -- masked L2
 reconstruction x20, masked L1 depth, ambient L1 x2.5, 1-cos light direction, grey-albedo L1 x5,
-GAN BCE x0.01, DSSIM x8/2.  Everything here is stock PyTorch-ROCm (consumer of the render block's
-outputs); the only hand-written device code on the step is the render block itself.
+GAN BCE x0.01, DSSIM x8/2.  The networks and the small loss terms are stock PyTorch-ROCm.  Hand-written device code on the
+step: the render block, and -- with TrainConfig.image_losses = "hip" -- the image-loss head that consumes its output (the mask
+paste, the masked L2's sums and the SSIM as one fused forward and one fused backward, `losses.image_losses`).
 
 Data parallelism: faces shard over ranks (whole faces per GPU, `shard_range`), the render block needs no
 collective, and the step adds one RCCL gradient all-reduce per optimiser step through
@@ -162,14 +163,22 @@ def synthetic_batch(B: int, seed0: int, H: int = 256, W: int = 256, device="cpu"
 # ------------------------------------------------------------------------------------------------
 # losses and the step
 # ------------------------------------------------------------------------------------------------
-def generator_losses(out, batch, logits_fake_for_g, ssim_stacked: bool = False, ssim_blur: str = "aten") -> Dict[str, torch.Tensor]:
-    """The seven generator-side terms of T8:633-645.  `out` is RelightNet.forward's 8-tuple."""
+def generator_losses(out, batch, logits_fake_for_g, ssim_stacked: bool = False, ssim_blur: str = "aten",
+                     image_terms=None) -> Dict[str, torch.Tensor]:
+    """The seven generator-side terms of T8:633-645.  `out` is RelightNet.forward's 8-tuple.
+    `image_terms`: the (composite, recon_sq_sum, mask_sum, ssim) of `losses.image_losses` for this `out` and `batch`; the
+    reconstruction and DSSIM terms are then formed from them (same scalar formulas) instead of from `rendered`, and `ssim_stacked` /
+    `ssim_blur` are not used."""
     albedo, depth, _w, _amb_l, _full, rendered, unit_light, ambient_values = out
     B = rendered.shape[0]
     img = batch["images"].permute(0, 3, 1, 2)
     m3 = batch["masks_fill"].permute(0, 3, 1, 2).expand(-1, 3, -1, -1)     # (a view: the reference's .repeat copies the mask three times, T8:619)
     L = {}
-    L["recon"] = 20.0 * F.mse_loss(rendered * m3, img * m3, reduction="sum") / m3.sum()                     # T8:633
+    if image_terms is None:
+        L["recon"] = 20.0 * F.mse_loss(rendered * m3, img * m3, reduction="sum") / m3.sum()                 # T8:633
+    else:
+        _composite, recon_sq_sum, mask_sum, ssim_bc = image_terms
+        L["recon"] = 20.0 * recon_sq_sum / mask_sum
     L["depth"] = F.l1_loss(depth.permute(0, 2, 3, 1) * batch["masks"], batch["depths"] * batch["masks"],
                            reduction="sum") / batch["masks"].sum()                                         # T8:634
     L["ambient"] = 2.5 * F.l1_loss(ambient_values, batch["lightings"][:, 0].reshape(B, 1, 1))               # T8:635
@@ -178,9 +187,12 @@ def generator_losses(out, batch, logits_fake_for_g, ssim_stacked: bool = False, 
     L["albedo"] = 5.0 * F.l1_loss(grey * batch["masks_fill"], batch["albedo"] * batch["masks_fill"],
                                   reduction="sum") / batch["masks_fill"].sum()                              # T8:639
     L["generator"] = 0.01 * F.binary_cross_entropy_with_logits(logits_fake_for_g, torch.ones_like(logits_fake_for_g))
-    composite = rendered * m3 + (1.0 - m3) * img
-    L["DSSIM"] = 8.0 * (1 - ssim(composite, img, data_range=1.0, size_average=True, nonnegative_ssim=True, stacked=ssim_stacked,
-                                blur_kernels=ssim_blur)) / 2.0
+    if image_terms is None:
+        composite = rendered * m3 + (1.0 - m3) * img
+        L["DSSIM"] = 8.0 * (1 - ssim(composite, img, data_range=1.0, size_average=True, nonnegative_ssim=True, stacked=ssim_stacked,
+                                    blur_kernels=ssim_blur)) / 2.0
+    else:
+        L["DSSIM"] = 8.0 * (1 - torch.relu(ssim_bc).mean(1).mean()) / 2.0      # `ssim`'s last three lines
     L["total"] = sum(L.values())
     return L
 
@@ -208,8 +220,20 @@ class TrainConfig:
                                 # 0.45 ms per step slower with MIOpen's kernels (profiles/r06_ssim_ab.txt): off
     ssim_blur: str = "aten"     # "aten": the SSIM's depthwise blurs through ATen's conv_depthwise2d kernels (`_DepthwiseBlur`);
                                 # "miopen": F.conv2d as in rounds 2-5 (CK grouped / naive solvers: ~3 ms per step more)
+    image_losses: str = "torch" # "hip": the mask paste, the masked L2's sums and the SSIM of the DSSIM term as one fused HIP forward and
+                                # one fused HIP backward (`losses.image_losses`); the one composite feeds the D step, PatchGAN's
+                                # generator pass and the DSSIM.  `ssim_blur` and `ssim_stacked` are ignored under "hip".
     render_pixels: str = "all"  # "mask": the render block leaves out the pixels outside the mask (RenderParams.pixels; every loss
                                 # multiplies them by the mask, T8:619-643: bit-equal losses, half the training march)
+
+
+    def __post_init__(self):
+        _check_image_losses(self)
+
+
+def _check_image_losses(cfg: "TrainConfig"):
+    if cfg.image_losses not in ("torch", "hip"):
+        raise ValueError("TrainConfig.image_losses must be 'torch' or 'hip', got %r" % (cfg.image_losses,))
 
 
 LAST_GATED_EPOCH = 14      # T8:245, 258, 271, 283: the decoders' skip additions switch on after epochs 8 / 10 / 12 / 14
@@ -306,7 +330,14 @@ class Trainer:
         m3 = batch["masks_fill"].permute(0, 3, 1, 2).expand(-1, 3, -1, -1)
         out = self.net(batch["images"], epoch, self.K, batch["masks_fill"])              # T8:618
         rendered = out[5]
-        composite = rendered * m3 + (1.0 - m3) * img
+        _check_image_losses(self.cfg)                                                    # (read at step time, as ssim_blur is)
+        image_terms = None
+        if self.cfg.image_losses == "hip":
+            from .losses import image_losses
+            image_terms = image_losses(rendered, batch["images"], batch["masks_fill"])
+            composite = image_terms[0]
+        else:
+            composite = rendered * m3 + (1.0 - m3) * img
         logs = {}
         # ---- discriminator (T8:617-629) ----
         if j % self.cfg.gd_ratio == 0:
@@ -321,7 +352,8 @@ class Trainer:
         for p in self.patchgan.parameters():
             p.requires_grad_(False)
         try:
-            L = generator_losses(out, batch, self.patchgan(composite), self.cfg.ssim_stacked, self.cfg.ssim_blur)
+            L = generator_losses(out, batch, self.patchgan(composite), self.cfg.ssim_stacked, self.cfg.ssim_blur,
+                                 image_terms=image_terms)
             L["total"].backward()
         finally:
             for p in self.patchgan.parameters():

@@ -380,6 +380,60 @@ int gcfr_masked_metrics_u8(const uint8_t *recon_u8, const uint8_t *gt_u8, const 
                            size_t workspace_bytes, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The training step's image-loss head: everything the step computes from `rendered_images` and the photograph
+ * between the render block and loss.backward() -- the mask paste, the masked reconstruction L2's sums and the SSIM of
+ * the DSSIM term -- as one fused forward and one fused backward (csrc/gcfr_losses.hip).
+ * ------------------------------------------------------------------------------------------- */
+
+/* layout of the photograph argument below */
+#define GCFR_IMAGES_NHWC 0 /* (B,H,W,3), as the training batch holds it (T8:618) */
+#define GCFR_IMAGES_NCHW 1 /* (B,3,H,W) */
+
+/*
+ * Forward.  Replaces train_raytracing_relighting_CelebAHQ_DSSIM_8x.py:619 and :641 (the paste, evaluated twice there),
+ * :633 (the two sums of the masked L2) and :643 (pytorch_msssim.ssim up to its per-channel mean):
+ *   rendered   (B,3,H,W) f32        rendered_images
+ *   images     (B,H,W,3) or (B,3,H,W) f32, by `images_layout`      the photograph
+ *   mask       (B,H,W) f32, any values, or NULL (no mask: m = 1)  mask_fill_nose_and_mouth
+ *   window     HOST, 11 f32         the normalised Gaussian window (sigma 1.5 in the reference); read during the call
+ *   data_range                      pytorch_msssim's data_range (1.0 at T8:643): C1 = (0.01 data_range)^2, C2 = (0.03 data_range)^2
+ *   composite  (B,3,H,W) f32        = rendered * m + (1 - m) * images, each operation separately rounded
+ *   ssim       (B,3) f32            the mean of the SSIM map over its (H-10) x (W-10) 'valid' positions, per image and
+ *                                   channel, BEFORE the relu (nonnegative_ssim) and the means over channels and images
+ *   sums       (2) f64              { sum (rendered m - images m)^2, sum m }, both over (B,3,H,W) as T8:633's mse_loss(...,
+ *                                   'sum') and mask.sum() on the mask repeated over the three channels
+ *   workspace  gcfr_image_losses_workspace_bytes(B,H,W) = 8 * (5 * B * ceil(H/16) * ceil(W/32) + 2 * B) bytes of device
+ *              scratch, 8-byte aligned (0 is returned for an unsupported shape); it need not be cleared
+ * C = 3 and the window of 11 are fixed; 11 <= H, W <= 4096 (any parity), 1 <= B <= 65535; anything else is
+ * GCFR_ERR_INVALID_ARGUMENT before a launch.
+ * Numerical contract: `composite` is bit-equal to the torch f32 expression; `ssim` is within 2e-6 relative, and `sums` within
+ * 2e-6 relative, of the same formulas evaluated in f64 on the f32 inputs (f32 blurs: the same sums of the same eleven products
+ * as a depthwise convolution's, filtered along H, then W; f32 terms added in f64).  Tile partials are reduced in f64 in a fixed
+ * order, without floating-point atomics: two calls on the same inputs return the same bits.
+ */
+size_t gcfr_image_losses_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int gcfr_image_losses_fwd(const float *rendered, const float *images, const float *mask, int32_t images_layout,
+                          int32_t B, int32_t H, int32_t W, const float *window, double data_range, float *composite,
+                          float *ssim, double *sums, void *workspace, size_t workspace_bytes, void *stream);
+
+/*
+ * Backward of the above with respect to `rendered` (what autograd replays for T8:619 / 633 / 641 / 643), gather form:
+ *   g_composite (B,3,H,W) f32 or NULL   dLoss/d composite (PatchGAN's gradient)
+ *   g_ssim      (B,3) f32 or NULL       dLoss/d ssim
+ *   g_recon     DEVICE (1) f32 or NULL  dLoss/d sums[0]
+ *   grad_rendered (B,3,H,W) f32 = m (g_composite + gX) + g_recon 2 m (rendered m - images m), with
+ *       gX = blurT(a) + 2 X blurT(b) + Y blurT(c);  X = composite, Y = images;  a, b, c = the adjoints of the SSIM map with
+ *       respect to blur(X), blur(X X), blur(X Y), scaled by g_ssim / ((H-10)(W-10)) and recomputed from the inputs;  blurT = the
+ *       same symmetric window applied to the zero-extended valid map.
+ * The other arguments as in the forward.  Contract: within 2e-5 of the gradient's largest entry of the f64 evaluation; every
+ * element is written once by one lane (no atomics): bit-reproducible.  grad_rendered must not alias an input.
+ */
+int gcfr_image_losses_bwd(const float *rendered, const float *images, const float *mask, int32_t images_layout,
+                          int32_t B, int32_t H, int32_t W, const float *window, double data_range,
+                          const float *g_composite, const float *g_ssim, const float *g_recon, float *grad_rendered,
+                          void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Measurement aid (bench.py `roofline.hbm_measured_copy_GBs`): a float4 grid-stride device-to-device copy of `bytes` bytes
  * (multiple of 16, both pointers 16-byte aligned), one workgroup of 256 lanes per CU, four loads in flight per lane, non-temporal --
  * the achievable-HBM probe (6.3 TB/s, read + write) the roofline's 8 TB/s spec peak is reported beside.  Not part of the render path.
