@@ -1,7 +1,10 @@
 """CPU: the image-loss head's plumbing (csrc/gcfr_losses.hip, include/gcfr.h, losses.py, TrainConfig.image_losses) -- the three
 symbols are declared, bound and exported; argument validation happens on the host before any launch; the workspace formula is the
 documented one; the switch validates its value; there is no CPU path; `generator_losses` without `image_terms` computes what it
-always did, and with torch-made terms the same numbers; the new kernels are spill-free in the built library."""
+always did, and with torch-made terms the same numbers; the new kernels are spill-free in the built library.
+And the numpy-f32 restatement of the kernel's operation order (tests/image_losses_emulation.py), which
+tests/test_gpu_image_losses_regimes.py holds the kernel to bit for bit, is itself held to the f64 restatement here, under the gates
+of tests/test_gpu_image_losses.py, so that it is a checked statement and not a second opinion."""
 import ctypes
 import os
 
@@ -144,3 +147,68 @@ def test_the_new_kernels_use_no_scratch(tmp_path):
     assert mine["image_losses_fwd_kernel"]["lds"] <= 160 * 1024 // 3        # three workgroups per CU
     assert mine["image_losses_bwd_kernel"]["lds"] <= 64 * 1024              # static LDS; two workgroups of 512 lanes per CU
     assert mine["image_losses_bwd_kernel"]["vgpr"] <= 128                   # 512 lanes per workgroup
+
+
+# ------------------------------------------------------------------------------------------------
+# the operation-order restatement (tests/image_losses_emulation.py) against the f64 one
+# ------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("mask", ["face", "fractional", "none"])
+@pytest.mark.parametrize("shape", [(2, 64, 40), (1, 33, 47)], ids=lambda s: "x".join(map(str, s)))
+def test_the_emulation_keeps_the_f64_gates_on_white_noise(shape, mask):
+    """No library call: white-noise inputs, masks, upstream gradients, the f64 reference and the gates (composite bit-equal to the
+    torch f32 expression; ssim / sq_sum / mask_sum 2e-6 relative; gradient 2e-5 of its largest entry for each upstream alone and for
+    all together) are those of tests/test_gpu_image_losses.py."""
+    import image_losses_emulation as E
+    import test_gpu_image_losses as G
+    B, H, W = shape
+    X, Y = G._pair(B, H, W)
+    M, ups = G._mask(mask, B, H, W), G._upstreams(B, H, W)
+    ref = G._reference(X, Y, M, ups)
+    win = E.gauss_window()
+    comp, s, sq, msum, smap = E.forward(X, Y, M, win, 1.0)
+    assert comp.dtype == s.dtype == smap.dtype == np.float32 and sq.dtype == msum.dtype == np.float64
+    assert smap.shape == (B, 3, H - 10, W - 10) and s.shape == (B, 3)
+    Gc, Gs, gq = ups
+    sel = dict(composite=dict(g_composite=Gc), ssim=dict(g_ssim=Gs), recon=dict(g_recon=gq),
+               all=dict(g_composite=Gc, g_ssim=Gs, g_recon=gq))
+    grads = {k: E.backward(X, Y, M, win, 1.0, **kw) for k, kw in sel.items()}
+    rel = lambda a, b: float(np.max(np.abs(np.asarray(a, np.float64) - b) / np.abs(b)))
+    e_s, e_sq, e_m = rel(s, ref["ssim"]), rel(sq, ref["sq"]), rel(msum, ref["msum"])
+    e_g = {k: float(np.abs(g.astype(np.float64) - ref["grads"][k]).max() / np.abs(ref["grads"][k]).max()) for k, g in grads.items()}
+    print("%s %s: ssim %.2e sq %.2e msum %.2e grad %s" % (shape, mask, e_s, e_sq, e_m, " ".join("%s %.2e" % kv for kv in sorted(e_g.items()))))
+    assert E.bit_equal(comp, ref["composite"])
+    assert e_s <= 2e-6 and e_sq <= 2e-6 and e_m <= 2e-6, (e_s, e_sq, e_m)
+    for k, e in e_g.items():
+        assert grads[k].dtype == np.float32 and np.abs(ref["grads"][k]).max() > 0
+        assert e <= 2e-5, (k, e)
+
+
+def test_the_emulation_refuses_anything_but_float32():
+    import image_losses_emulation as E
+    win = E.gauss_window()
+    assert win.dtype == np.float32 and win.shape == (11,) and np.array_equal(win, win[::-1])      # symmetric: blurT reuses it unflipped
+    X = np.full((1, 3, 11, 11), 0.5, np.float32)
+    for bad in (dict(rendered=X.astype(np.float64)), dict(images_nchw=X.astype(np.float64)), dict(window=win.astype(np.float64)),
+                dict(mask=np.ones((1, 11, 11)))):
+        with pytest.raises(AssertionError):
+            E.forward(**{**dict(rendered=X, images_nchw=X, mask=None, window=win), **bad})
+    with pytest.raises(AssertionError):
+        E.backward(X, X, None, win, g_ssim=np.ones((1, 3)))
+    with pytest.raises(AssertionError):
+        E.backward(X, X, None, win, g_recon=0.37)
+    C1, C2 = E.consts(1.0)
+    assert C1.dtype == C2.dtype == np.float32 and C1 == np.float32(1e-4) and C2 == np.float32(9e-4)
+
+
+def test_the_emulations_ulp_distance_and_bit_comparison():
+    import image_losses_emulation as E
+    one = np.float32(1.0)
+    up = np.nextafter(one, np.float32(2.0))
+    assert E.ulps(one, one) == 0 and E.ulps(one, up) == 1 and E.ulps(-one, -up) == 1
+    assert E.ulps(np.float32(0.0), np.float32(-0.0)) == 0
+    assert E.ulps(np.nextafter(np.float32(0), one), -np.nextafter(np.float32(0), one)) == 2
+    a = np.array([1.0, np.nan, 0.0], np.float32)
+    assert E.bit_equal(a, a.copy())
+    assert not E.bit_equal(a, np.array([up, np.nan, 0.0], np.float32))
+    assert not E.bit_equal(a, np.array([1.0, 2.0, 0.0], np.float32))
+    assert not E.bit_equal(a, np.array([1.0, np.nan, -0.0], np.float32))
