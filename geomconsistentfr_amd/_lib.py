@@ -105,6 +105,10 @@ _SIGNATURES = {
     "gcfr_image_losses_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
     "gcfr_image_losses_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _d, _p, _p, _p, _p, ctypes.c_size_t, _p]),
     "gcfr_image_losses_bwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _d, _p, _p, _p, _p, _p]),
+    "gcfr_supervised_losses_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i]),
+    "gcfr_supervised_losses_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, ctypes.c_int64, _i, _i, _i, _p, _p, _p, ctypes.c_size_t, _p]),
+    "gcfr_supervised_losses_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, ctypes.c_int64, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p,
+                                        _p, _p, _p, _p]),
     "gcfr_copy_probe": (_i, [_p, _p, ctypes.c_size_t, _p]),
 }
 

@@ -164,11 +164,13 @@ def synthetic_batch(B: int, seed0: int, H: int = 256, W: int = 256, device="cpu"
 # losses and the step
 # ------------------------------------------------------------------------------------------------
 def generator_losses(out, batch, logits_fake_for_g, ssim_stacked: bool = False, ssim_blur: str = "aten",
-                     image_terms=None) -> Dict[str, torch.Tensor]:
+                     image_terms=None, supervised_terms=None) -> Dict[str, torch.Tensor]:
     """The seven generator-side terms of T8:633-645.  `out` is RelightNet.forward's 8-tuple.
     `image_terms`: the (composite, recon_sq_sum, mask_sum, ssim) of `losses.image_losses` for this `out` and `batch`; the
     reconstruction and DSSIM terms are then formed from them (same scalar formulas) instead of from `rendered`, and `ssim_stacked` /
-    `ssim_blur` are not used."""
+    `ssim_blur` are not used.
+    `supervised_terms`: the (5,) tensor of `losses.supervised_losses` for this `out`, `batch` and `logits_fake_for_g`; the depth,
+    ambient, lighting, albedo and generator entries are then its five elements (`logits_fake_for_g` is not used)."""
     albedo, depth, _w, _amb_l, _full, rendered, unit_light, ambient_values = out
     B = rendered.shape[0]
     img = batch["images"].permute(0, 3, 1, 2)
@@ -179,14 +181,17 @@ def generator_losses(out, batch, logits_fake_for_g, ssim_stacked: bool = False, 
     else:
         _composite, recon_sq_sum, mask_sum, ssim_bc = image_terms
         L["recon"] = 20.0 * recon_sq_sum / mask_sum
-    L["depth"] = F.l1_loss(depth.permute(0, 2, 3, 1) * batch["masks"], batch["depths"] * batch["masks"],
-                           reduction="sum") / batch["masks"].sum()                                         # T8:634
-    L["ambient"] = 2.5 * F.l1_loss(ambient_values, batch["lightings"][:, 0].reshape(B, 1, 1))               # T8:635
-    L["lighting"] = torch.sum(1 - torch.sum(unit_light * batch["lightings"][:, 1:4].reshape(B, 3, 1, 1), dim=1)) / B
-    grey = albedo.mean(1).reshape(B, albedo.shape[2], albedo.shape[3], 1)
-    L["albedo"] = 5.0 * F.l1_loss(grey * batch["masks_fill"], batch["albedo"] * batch["masks_fill"],
-                                  reduction="sum") / batch["masks_fill"].sum()                              # T8:639
-    L["generator"] = 0.01 * F.binary_cross_entropy_with_logits(logits_fake_for_g, torch.ones_like(logits_fake_for_g))
+    if supervised_terms is None:
+        L["depth"] = F.l1_loss(depth.permute(0, 2, 3, 1) * batch["masks"], batch["depths"] * batch["masks"],
+                               reduction="sum") / batch["masks"].sum()                                         # T8:634
+        L["ambient"] = 2.5 * F.l1_loss(ambient_values, batch["lightings"][:, 0].reshape(B, 1, 1))               # T8:635
+        L["lighting"] = torch.sum(1 - torch.sum(unit_light * batch["lightings"][:, 1:4].reshape(B, 3, 1, 1), dim=1)) / B
+        grey = albedo.mean(1).reshape(B, albedo.shape[2], albedo.shape[3], 1)
+        L["albedo"] = 5.0 * F.l1_loss(grey * batch["masks_fill"], batch["albedo"] * batch["masks_fill"],
+                                      reduction="sum") / batch["masks_fill"].sum()                              # T8:639
+        L["generator"] = 0.01 * F.binary_cross_entropy_with_logits(logits_fake_for_g, torch.ones_like(logits_fake_for_g))
+    else:
+        L["depth"], L["ambient"], L["lighting"], L["albedo"], L["generator"] = supervised_terms.unbind()
     if image_terms is None:
         composite = rendered * m3 + (1.0 - m3) * img
         L["DSSIM"] = 8.0 * (1 - ssim(composite, img, data_range=1.0, size_average=True, nonnegative_ssim=True, stacked=ssim_stacked,
@@ -225,15 +230,23 @@ class TrainConfig:
                                 # generator pass and the DSSIM.  `ssim_blur` and `ssim_stacked` are ignored under "hip".
     render_pixels: str = "all"  # "mask": the render block leaves out the pixels outside the mask (RenderParams.pixels; every loss
                                 # multiplies them by the mask, T8:619-643: bit-equal losses, half the training march)
+    supervised_losses: str = "torch"  # "hip": the depth, ambient, lighting, albedo and generator terms (T8:634-642) as one fused HIP
+                                # forward and one fused HIP backward (`losses.supervised_losses`); independent of `image_losses`
 
 
     def __post_init__(self):
         _check_image_losses(self)
+        _check_supervised_losses(self)
 
 
 def _check_image_losses(cfg: "TrainConfig"):
     if cfg.image_losses not in ("torch", "hip"):
         raise ValueError("TrainConfig.image_losses must be 'torch' or 'hip', got %r" % (cfg.image_losses,))
+
+
+def _check_supervised_losses(cfg: "TrainConfig"):
+    if cfg.supervised_losses not in ("torch", "hip"):
+        raise ValueError("TrainConfig.supervised_losses must be 'torch' or 'hip', got %r" % (cfg.supervised_losses,))
 
 
 LAST_GATED_EPOCH = 14      # T8:245, 258, 271, 283: the decoders' skip additions switch on after epochs 8 / 10 / 12 / 14
@@ -331,6 +344,7 @@ class Trainer:
         out = self.net(batch["images"], epoch, self.K, batch["masks_fill"])              # T8:618
         rendered = out[5]
         _check_image_losses(self.cfg)                                                    # (read at step time, as ssim_blur is)
+        _check_supervised_losses(self.cfg)
         image_terms = None
         if self.cfg.image_losses == "hip":
             from .losses import image_losses
@@ -352,8 +366,13 @@ class Trainer:
         for p in self.patchgan.parameters():
             p.requires_grad_(False)
         try:
-            L = generator_losses(out, batch, self.patchgan(composite), self.cfg.ssim_stacked, self.cfg.ssim_blur,
-                                 image_terms=image_terms)
+            logits = self.patchgan(composite)
+            supervised_terms = None
+            if self.cfg.supervised_losses == "hip":
+                from .losses import supervised_losses
+                supervised_terms = supervised_losses(out[1], out[0], out[6], out[7], batch, logits)
+            L = generator_losses(out, batch, logits, self.cfg.ssim_stacked, self.cfg.ssim_blur, image_terms=image_terms,
+                                 supervised_terms=supervised_terms)
             L["total"].backward()
         finally:
             for p in self.patchgan.parameters():

@@ -471,6 +471,68 @@ int gcfr_image_losses_bwd(const float *rendered, const float *images, const floa
                           void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The training step's supervised-loss head: the five generator-side terms that do NOT read `rendered_images` -- the masked
+ * depth L1, the ambient L1, the 1 - cos lighting term, the masked grey-albedo L1 and the generator's BCE -- as one fused forward
+ * (plus one finishing launch) and one fused backward (csrc/gcfr_supervised_losses.hip).
+ * ------------------------------------------------------------------------------------------- */
+
+/*
+ * Forward.  Replaces train_raytracing_relighting_CelebAHQ_DSSIM_8x.py:634 (depth), :635 (ambient), :636 (lighting), :638-639
+ * (grey albedo) and :642 (BCE of PatchGAN's logits against ones).  All planes contiguous f32:
+ *   depth          (B,1,H,W)          the network's depth
+ *   gt_depth, mask (B,H,W,1)          batch depths and skin masks (the same memory order as depth)
+ *   albedo         (B,3,H,W)          the network's albedo
+ *   gt_albedo, mask_fill (B,H,W,1)    batch grey albedo and mask_fill_nose_and_mouth
+ *   unit_light     (B,3)              unit_light_direction (B,3,1,1)
+ *   ambient_values (B)                (B,1,1)
+ *   lightings      (B,4)              batch lightings: [ambient, light direction]
+ *   logits         (n_logits) or NULL PatchGAN's output for the composite; NULL: terms[4] is exactly 0 (n_logits is ignored)
+ *   terms          (5) f32            depth, ambient, lighting, albedo, generator -- `generator_losses`' order:
+ *                                     S_d / M,  2.5 (A / B),  L / B,  5 (S_a / M_f),  0.01 (G / n_logits), f32 operations on the
+ *                                     f64 sums rounded to f32; an all-zero mask gives 0 / 0 = NaN, as torch does
+ *   sums           (4) f64            { S_d = sum |depth m - gt_depth m|, M = sum m, S_a = sum |grey mf - gt_albedo mf|,
+ *                                     M_f = sum mf }; the backward reads M and M_f from here
+ *   workspace      gcfr_supervised_losses_workspace_bytes(B,H,W) = 8 * 5 * ceil(B H W / 1024) bytes of device scratch, 8-byte
+ *                  aligned (0 is returned for an unsupported shape); it need not be cleared
+ * 1 <= B <= 65535, 1 <= H, W <= 4096, B H W < 2^31, 1 <= n_logits < 2^31; anything else is GCFR_ERR_INVALID_ARGUMENT before a
+ * launch.
+ * Numerical contract: the stated operation order, exactly.  Per pixel, each one IEEE f32 operation (no contraction):
+ * |depth m - gt_depth m|;  grey = ((a0 + a1) + a2) * (1.0f / 3.0f), |grey mf - gt_albedo mf|.  Per image:
+ * |ambient_b - lightings[b,0]|;  1 - ((u0 l1 + u1 l2) + u2 l3).  Per logit, in f64: max(-x, 0) + log1p(exp(-|x|)).  The addends
+ * are summed in f64 in a fixed order (lanes, waves, workgroups; no floating-point atomics): two calls return the same bits, and
+ * the f32 restatement of this order (tests/supervised_losses_emulation.py) reproduces the terms to one ulp, the association of
+ * the f64 sums being the only freedom.  Planes are read with 16-byte loads when H W is a multiple of 4 and every plane pointer is
+ * 16-byte aligned, with 4-byte loads otherwise (same results).
+ */
+size_t gcfr_supervised_losses_workspace_bytes(int32_t B, int32_t H, int32_t W);
+int gcfr_supervised_losses_fwd(const float *depth, const float *gt_depth, const float *mask, const float *albedo,
+                               const float *gt_albedo, const float *mask_fill, const float *unit_light,
+                               const float *ambient_values, const float *lightings, const float *logits, int64_t n_logits,
+                               int32_t B, int32_t H, int32_t W, float *terms, double *sums, void *workspace,
+                               size_t workspace_bytes, void *stream);
+
+/*
+ * Backward of the above (what autograd replays for T8:634-639 and :642), one launch, every element written once:
+ *   sums                       the forward's (M and M_f are read from it on the device)
+ *   g_depth ... g_generator    DEVICE (1) f32 each or NULL: dLoss/d terms[0..4]; NULL writes zeros for that term's gradient
+ *   grad_depth (B,1,H,W)       = ((g_depth / M) sgn(depth m - gt_depth m)) m
+ *   grad_albedo (B,3,H,W)      = ((((g_albedo 5) / M_f) sgn(grey mf - gt_albedo mf)) mf) * (1.0f / 3.0f), the same in the three channels
+ *   grad_ambient_values (B)    = ((g_ambient 2.5) / B) sgn(ambient_b - lightings[b,0])
+ *   grad_unit_light (B,3)      = (-(g_lighting / B)) lightings[b,1+c]
+ *   grad_logits (n_logits)     = ((g_generator 0.01) / n_logits) (-(1 / (1 + e^x))); required when logits is given, untouched otherwise
+ * sgn(0) = 0 (and sgn(NaN) = 0), M and M_f rounded to f32, each operation one IEEE f32 operation, left to right; e^x is
+ * evaluated from plain f32 operations (clamp to [-87, 88], Cody-Waite reduction, a degree-5 polynomial, ldexp), within ~2 ulp.
+ * Bit-reproducible, and bit-equal to the f32 restatement of this order (tests/supervised_losses_emulation.py).  No output may
+ * alias an input.
+ */
+int gcfr_supervised_losses_bwd(const float *depth, const float *gt_depth, const float *mask, const float *albedo,
+                               const float *gt_albedo, const float *mask_fill, const float *ambient_values,
+                               const float *lightings, const float *logits, int64_t n_logits, int32_t B, int32_t H, int32_t W,
+                               const double *sums, const float *g_depth, const float *g_ambient, const float *g_lighting,
+                               const float *g_albedo, const float *g_generator, float *grad_depth, float *grad_albedo,
+                               float *grad_unit_light, float *grad_ambient_values, float *grad_logits, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Measurement aid (bench.py `roofline.hbm_measured_copy_GBs`): a float4 grid-stride device-to-device copy of `bytes` bytes
  * (multiple of 16, both pointers 16-byte aligned), one workgroup of 256 lanes per CU, four loads in flight per lane, non-temporal --
  * the achievable-HBM probe (6.3 TB/s, read + write) the roofline's 8 TB/s spec peak is reported beside.  Not part of the render path.

@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """What BASELINE configs[2]'s training step (batch 32, ~33 ms) is made of  (round-5 verdict: "the step nobody has opened").
 
-  tools/train_breakdown.py run [--steps 10] [--faces 32] [--image-losses {torch,hip}] [--levers ...]      (GPU)  warm-up, then `steps` steps between two
+  tools/train_breakdown.py run [--steps 10] [--faces 32] [--image-losses {torch,hip}] [--supervised-losses {torch,hip}] [--levers ...]      (GPU)  warm-up, then `steps` steps between two
         SENTINEL launches (gcfr_copy_probe: a kernel name that appears nowhere else in the step), each step's phases
         bracketed by in-stream events (no synchronisation inside the window): hourglass forward, render block forward, D
         step, G losses (+ PatchGAN forward), G backward, G optimiser.  Prints one JSON line (phase ms per step).
@@ -37,7 +37,8 @@ def run(a):
 
     dev = torch.device("cuda:0")
     torch.manual_seed(1234)
-    tr = Trainer(TrainConfig(ssim_stacked=bool(a.ssim_stacked), ssim_blur=a.ssim_blur, image_losses=a.image_losses), device=dev)
+    tr = Trainer(TrainConfig(ssim_stacked=bool(a.ssim_stacked), ssim_blur=a.ssim_blur, image_losses=a.image_losses,
+                            supervised_losses=a.supervised_losses), device=dev)
     batch = synthetic_batch(a.faces, 0, device=dev)
     for j in range(a.warmup):
         tr.step(batch, a.epoch, j, log=False)
@@ -106,7 +107,13 @@ def run(a):
         tr.opt.zero_grad(set_to_none=True)
         for p in tr.patchgan.parameters():
             p.requires_grad_(False)
-        Ls = generator_losses(out, batch, tr.patchgan(composite), tr.cfg.ssim_stacked, tr.cfg.ssim_blur, image_terms=image_terms)
+        logits = tr.patchgan(composite)
+        supervised_terms = None
+        if tr.cfg.supervised_losses == "hip":    # (as Trainer.step)
+            from geomconsistentfr_amd.losses import supervised_losses
+            supervised_terms = supervised_losses(out[1], out[0], out[6], out[7], batch, logits)
+        Ls = generator_losses(out, batch, logits, tr.cfg.ssim_stacked, tr.cfg.ssim_blur, image_terms=image_terms,
+                              supervised_terms=supervised_terms)
         ev.append(mark())
         Ls["total"].backward()
         for p in tr.patchgan.parameters():
@@ -121,7 +128,8 @@ def run(a):
     opened_ms = 1e3 * (time.perf_counter() - t0) / a.steps
     phases = {n: float(np.mean([m[i].elapsed_time(m[i + 1]) for m in marks])) for i, n in enumerate(names)}
     d_steps = sum(1 for j in range(a.steps) if j % tr.cfg.gd_ratio == 0)
-    print(json.dumps({"faces": a.faces, "steps": a.steps, "epoch": a.epoch, "image_losses": a.image_losses, "step_ms_plain": plain_ms, "step_ms_opened": opened_ms,
+    print(json.dumps({"faces": a.faces, "steps": a.steps, "epoch": a.epoch, "image_losses": a.image_losses, "supervised_losses": a.supervised_losses,
+                      "step_ms_plain": plain_ms, "step_ms_opened": opened_ms,
                       "phase_ms_per_step": phases, "d_steps_in_window": d_steps, "phase_names": names,
                       "phase_sentinels": bool(a.phase_sentinels),
                       "note": "in-stream events, no synchronisation inside the window; d_step is averaged over ALL steps (it runs "
@@ -134,6 +142,7 @@ def run(a):
 CLASSES = [
     # (class, regex on the kernel name) -- first match wins
     ("HIP image-loss head (gcfr::image_losses_)", r"gcfr::image_losses_"),
+    ("HIP supervised-loss head (gcfr::supervised_losses_)", r"gcfr::supervised_losses_"),
     ("HIP render block (gcfr::)", r"gcfr::"),
     ("BatchNorm (MIOpen)", r"[Bb]atch[Nn]orm"),
     ("depthwise conv (ATen: the SSIM's blurs)", r"DepthwiseConv|depthwise|conv_depthwise"),
@@ -290,6 +299,8 @@ def main():
     r.add_argument("--epoch", type=int, default=200)
     r.add_argument("--ssim-blur", choices=["aten", "miopen"], default="aten", help="TrainConfig.ssim_blur")
     r.add_argument("--image-losses", choices=["torch", "hip"], default="torch", help="TrainConfig.image_losses (hip: the fused image-loss head)")
+    r.add_argument("--supervised-losses", choices=["torch", "hip"], default="torch",
+                   help="TrainConfig.supervised_losses (hip: the fused supervised-loss head)")
     r.add_argument("--ssim-stacked", type=int, default=0, help="TrainConfig.ssim_stacked (0: the five separate blurs of rounds 2-5)")
     r.add_argument("--phase-sentinels", action="store_true", help="a sentinel launch at every phase boundary (classify then splits by phase)")
     c = sub.add_parser("classify")
