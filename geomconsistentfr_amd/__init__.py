@@ -6,5 +6,6 @@ as hand-written HIP kernels for gfx950 behind a C ABI (include/gcfr.h), plus the
 the reference's only callable boundary, RelightNet.forward.
 """
 from .block import RenderParams, render, shadow_min_distance, light_prep  # noqa: F401
+from .lighting import area_light, combine_lights, render_rig_from_depth  # noqa: F401
 
 __version__ = "0.5.0"   # = the library's (gcfr_version(): "gcfr-hip 0.5.0 gfx950")

@@ -109,6 +109,8 @@ _SIGNATURES = {
     "gcfr_supervised_losses_fwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, _p, ctypes.c_int64, _i, _i, _i, _p, _p, _p, ctypes.c_size_t, _p]),
     "gcfr_supervised_losses_bwd": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _p, ctypes.c_int64, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p, _p,
                                         _p, _p, _p, _p]),
+    "gcfr_light_rig_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "gcfr_light_rig_bwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
     "gcfr_copy_probe": (_i, [_p, _p, ctypes.c_size_t, _p]),
 }
 

@@ -137,6 +137,53 @@ def relight_lights(model, images, mask_u8, lights, ambient: float = 0.5, focal: 
     return relight_lights_device(model, images, mask_u8, lights, ambient, focal, device, fix_border, composite_mask_u8, epoch).cpu().numpy()
 
 
+def _as_light_rgb(light_rgb, device) -> torch.Tensor:
+    """a rig's colour x weight per light as a contiguous f32 device tensor (1|B,L,3); (L,3) is one rig shared by all faces"""
+    t = (light_rgb if torch.is_tensor(light_rgb) else torch.as_tensor(np.asarray(light_rgb, np.float32))).to(device=device, dtype=torch.float32)
+    return (t[None] if t.dim() == 2 else t).contiguous()
+
+
+def _rig_composites(x, out, cm, light_rgb, transfer: bool, fix_border: bool) -> torch.Tensor:
+    """`forward_lights`' tuple -> (B,H,W,3) uint8: the rig stage on its albedo (out[0]) and final shading (out[8]), then the image
+    kernel at one image per photograph and the optional border fix"""
+    from .lighting import combine_lights
+    rendered, _ = combine_lights(out[8], out[0], light_rgb)
+    imgs = pp.inference_images_device(x, rendered, cm, mask_f32=transfer)["rendered_image"]
+    return pp.fix_border_artifacts_device(imgs, cm) if fix_border else imgs
+
+
+@torch.no_grad()
+def relight_rig_device(model, images, mask_u8, lights, light_rgb, ambient: float = 0.5, focal: float = None, device="cuda",
+                       fix_border: bool = False, composite_mask_u8=None, epoch: int = 200) -> torch.Tensor:
+    """`relight_rig` up to the bytes ON THE DEVICE: (B,H,W,3) uint8 tensor, nothing copied back.  `images` / `mask_u8` / `lights` /
+    `light_rgb` may already be device tensors."""
+    x = _as_batch(images).to(device)
+    B, H, W, _ = x.shape
+    transfer = _is_transfer(model)
+    K = camera_matrix((700.0 if transfer else 1570.0) if focal is None else focal, H, W)          # host: read without a sync
+    as_u8 = lambda m: (m if torch.is_tensor(m) else torch.as_tensor(np.asarray(m))).to(device=device, dtype=torch.uint8)
+    m_u8 = as_u8(mask_u8)
+    mask = (m_u8.to(torch.float64).reshape(H, W, 1) / 255.0)                                                     # S1:580 / SLT:540
+    lights = (lights if torch.is_tensor(lights) else torch.as_tensor(np.asarray(lights, np.float32))).to(device=device, dtype=torch.float32)
+    lights = lights.reshape(-1, 3) if lights.dim() <= 2 else lights
+    out = model.forward_lights(x, epoch, K, mask, lights, float(ambient)) if transfer else model.forward_lights(x, epoch, K, mask, lights)
+    cm = m_u8 if composite_mask_u8 is None else as_u8(composite_mask_u8)
+    return _rig_composites(x, out, cm, _as_light_rgb(light_rgb, x.device), transfer, fix_border)
+
+
+@torch.no_grad()
+def relight_rig(model, images, mask_u8, lights, light_rgb, ambient: float = 0.5, focal: float = None, device="cuda",
+                fix_border: bool = False, composite_mask_u8=None, epoch: int = 200) -> np.ndarray:
+    """Every face of `images` (B,H,W,3) under the RIG of `lights` (L,3) | (B,L,3) with colour x weight `light_rgb` (L,3) | (1,L,3)
+    | (B,L,3) per light -- an area light (`lighting.area_light`), a coloured key / fill / rim set -- as ONE (B,H,W,3) uint8 RGB
+    composite per face.  One network pass (`forward_lights`), then `lighting.combine_lights` on its albedo and final shading
+    (the weights apply to the whole per-light shading, ambient included: weights that sum to 1 count the ambient once), the image
+    kernel and the optional border fix.  `model` / `ambient` / `focal` as in `relight_lights`; with one light of colour 1 the
+    composite equals `relight_lights(...)[:, 0]`.  One device-to-host copy of B*H*W*3 bytes at the end."""
+    return relight_rig_device(model, images, mask_u8, lights, light_rgb, ambient, focal, device, fix_border, composite_mask_u8,
+                              epoch).cpu().numpy()
+
+
 def fold_batchnorm(model):
     """An EVAL-mode copy of a RelightNet* model with every BatchNorm folded into the convolution in front of it.
 
@@ -192,11 +239,14 @@ class RelightSession:
     `miopen_find=True`: the warm-up passes run with `torch.backends.cudnn.benchmark` on, so MIOpen SEARCHES the fastest solver
     for each of the network's convolutions at this batch size (once per process and shape: seconds to a minute or two of
     construction time on a cold kernel cache) and the capture then holds those solvers instead of the immediate-mode
-    heuristic's picks; the flag is restored afterwards."""
+    heuristic's picks; the flag is restored afterwards.
+    `light_rgb` (L,3) | (1,L,3) | (B,L,3): the L lights are a RIG with this colour x weight per light (`relight_rig_device`): the
+    captured pass ends in the rig stage (lighting.combine_lights) and `run()` returns ONE composite per face, (B,H,W,3).  None
+    (the default): nothing changes."""
 
     def __init__(self, model, B: int, mask_u8, lights, ambient: float = 0.5, focal: float = None, device="cuda",
                  H: int = 256, W: int = 256, fix_border: bool = False, composite_mask_u8=None, graph: bool = True, epoch: int = 200,
-                 miopen_find: bool = False):
+                 miopen_find: bool = False, light_rgb=None):
         self.model, self.device, self.epoch, self.ambient, self.fix_border = model, torch.device(device), epoch, float(ambient), fix_border
         self.transfer = _is_transfer(model)
         self.K = camera_matrix((700.0 if self.transfer else 1570.0) if focal is None else focal, H, W)       # host
@@ -206,6 +256,7 @@ class RelightSession:
         self.mask = (self.m_u8.to(torch.float64).reshape(H, W, 1) / 255.0)
         lights = (lights if torch.is_tensor(lights) else torch.as_tensor(np.asarray(lights, np.float32))).to(device=self.device, dtype=torch.float32)
         self.lights = (lights.reshape(-1, 3) if lights.dim() <= 2 else lights).contiguous()
+        self.light_rgb = None if light_rgb is None else _as_light_rgb(light_rgb, self.device)     # a rig: one composite per face
         self.x = torch.zeros((B, H, W, 3), dtype=torch.float32, device=self.device)
         self.ambient_dev = torch.full((1,), self.ambient, dtype=torch.float32, device=self.device)   # (no host-to-device copy inside the capture)
         self.out = None
@@ -239,6 +290,8 @@ class RelightSession:
                 o = self.model.forward_lights(self.x, self.epoch, self.K, self.mask, self.lights)
         finally:
             self.model.hoist_prepass = hoist
+        if self.light_rgb is not None:
+            return _rig_composites(self.x, o, self.cm, self.light_rgb, self.transfer, self.fix_border)
         imgs = pp.inference_images_device(self.x, o[5], self.cm, mask_f32=self.transfer)["rendered_image"]
         if self.fix_border:
             B, L, H, W, _ = imgs.shape
@@ -248,7 +301,7 @@ class RelightSession:
     @torch.no_grad()
     def run(self, images=None) -> torch.Tensor:
         """images (B,H,W,3) f32 in [0,1] (host or device; None = whatever the static input holds) -> (B,L,H,W,3) uint8 DEVICE
-        tensor; with a graph it is overwritten by the next run."""
+        tensor ((B,H,W,3) for a session built with `light_rgb`); with a graph it is overwritten by the next run."""
         if images is not None:
             self.x.copy_(_as_batch(images), non_blocking=True)
         if self.graph is None:

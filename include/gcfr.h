@@ -533,6 +533,55 @@ int gcfr_supervised_losses_bwd(const float *depth, const float *gt_depth, const 
                                float *grad_unit_light, float *grad_ambient_values, float *grad_logits, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * The light-rig stage: the L per-light shadings of the many-lights path combined, with a colour x weight per light, into ONE relit
+ * image per face (an area light as a cone of directions, a coloured key / fill / rim set, a sampled environment), as one forward
+ * and one backward launch (csrc/gcfr_light_rig.hip).  No existing entry point changes: the stage reads the `final` plane that
+ * gcfr_render_fwd / gcfr_render_from_depth_fwd write, and its g_final is what gcfr_render_bwd accepts as `g_final`.
+ * ------------------------------------------------------------------------------------------- */
+
+/*
+ * Forward, one launch.  All planes contiguous f32:
+ *   final_shading (B,L,H,W)            the many-lights `final` (T8:518 per light)
+ *   albedo        (B,3,H,W)
+ *   rgb           (rgb_batch,L,3)      colour x weight of every light; rgb_batch = B (a rig per face) or 1 (one rig for all faces)
+ *   rendered      (B,3,H,W) out  =     albedo[b,c,p] * shading_rgb[b,c,p]
+ *   shading_rgb   (B,3,H,W) out  =     sum_l rgb[b,l,c] * final_shading[b,l,p];  may be NULL (then it is not written)
+ * The colour weights the whole per-light shading, its ambient term included: weights that sum to 1 count the ambient once.
+ * B >= 1, 1 <= L <= 4096, H, W >= 1 (any parity) with H W < 2^31 and B ceil(H W / 1024) < 2^31, rgb_batch = 1 or B; anything else,
+ * or a NULL among final_shading / albedo / rgb / rendered, is GCFR_ERR_INVALID_ARGUMENT before a launch.
+ * Numerical contract: the stated operation order, exactly.  Every product and sum is one IEEE f32 operation (no contraction):
+ * acc = rgb[0,c] final[0]; acc = acc + rgb[l,c] final[l] for l = 1 .. L-1 in ascending order (no add to zero); rendered = albedo acc.
+ * Nothing is clamped (negative and zero weights are legal) and non-finite values propagate as IEEE arithmetic propagates them.
+ * Bit-reproducible, and bit-equal to the f32 restatement of this order (tests/light_rig_emulation.py); at L = 1 and rgb = 1 it is
+ * gcfr_shade_fwd's composite.  Planes are read and written with 16-byte accesses when H W is a multiple of 4 and every plane pointer
+ * is 16-byte aligned, with 4-byte accesses otherwise (same results).  The uint8 composite is not written here: pass `rendered` to
+ * gcfr_inference_images_u8 with L = 1.  No output may alias an input.
+ */
+int gcfr_light_rig_fwd(const float *final_shading, const float *albedo, const float *rgb, int32_t rgb_batch, int32_t B, int32_t L,
+                       int32_t H, int32_t W, float *rendered, float *shading_rgb, void *stream);
+
+/*
+ * Backward of the above, one launch.  final_shading, albedo, rgb and the shape as in the forward (shading_rgb is recomputed, the
+ * forward's copy is not read):
+ *   g_rendered    (B,3,H,W) f32 or NULL   dLoss/d rendered
+ *   g_shading_rgb (B,3,H,W) f32 or NULL   dLoss/d shading_rgb; at least one of the two must be given.  With
+ *                                         u[c] = g_shading_rgb[c] + g_rendered[c] * albedo[c] (an absent term is not formed):
+ *   g_final  (B,L,H,W) f32 or NULL    =   (rgb[b,l,0] u[0] + rgb[b,l,1] u[1]) + rgb[b,l,2] u[2]
+ *   g_albedo (B,3,H,W) f32 or NULL    =   g_rendered[c] * shading_rgb[c]  (zeros without g_rendered)
+ *   g_rgb    (rgb_batch,L,3) F64 or NULL  +=  sum_p final_shading[b,l,p] u[c,p], for rgb_batch = 1 also summed over b.  ACCUMULATED:
+ *                                         the caller clears it (as grad_light_pt / grad_ambient of gcfr_render_bwd) and rounds to f32
+ * At least one output must be given; a NULL output is skipped.  Each f32 product and sum is one IEEE operation in the stated order,
+ * channels 0, 1, 2, the first product initialising: g_final and g_albedo are bit-reproducible and bit-equal to the f32 restatement.
+ * g_rgb: a lane adds the (exact) f64 products of its four pixels, a wave reduces them through a shuffle tree, the workgroup adds
+ * the waves' sums in LDS and adds its totals to g_rgb with one f64 atomic per entry (wave reduction + f64 atomics, no finishing
+ * pass): the order of these f64 additions is free, so two calls may differ in the last bits of the f64 sum -- after the rounding to
+ * f32, by one ulp of sum_p |final_shading u| at the most.
+ */
+int gcfr_light_rig_bwd(const float *final_shading, const float *albedo, const float *rgb, int32_t rgb_batch, int32_t B, int32_t L,
+                       int32_t H, int32_t W, const float *g_rendered, const float *g_shading_rgb, float *g_final, float *g_albedo,
+                       double *g_rgb, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Measurement aid (bench.py `roofline.hbm_measured_copy_GBs`): a float4 grid-stride device-to-device copy of `bytes` bytes
  * (multiple of 16, both pointers 16-byte aligned), one workgroup of 256 lanes per CU, four loads in flight per lane, non-temporal --
  * the achievable-HBM probe (6.3 TB/s, read + write) the roofline's 8 TB/s spec peak is reported beside.  Not part of the render path.
