@@ -8,7 +8,7 @@ runtime, so device pointers and streams are shared between torch and the kernels
 import ctypes
 import os
 
-import torch  # noqa: F401  (must be loaded before libgcfr_hip.so, see above)
+import torch  # (must be loaded before libgcfr_hip.so, see above)
 
 from . import build as _build
 
@@ -174,3 +174,23 @@ def exported_symbols():
 def check(status: int, what: str):
     if status != GCFR_OK:
         raise GcfrError("%s failed: %s (%d)" % (what, _ERRORS.get(status, "unknown"), status))
+
+
+def require_device(*tensors):
+    for t in tensors:
+        if t is not None and not t.is_cuda:
+            raise GcfrError("geomconsistentfr_amd has no CPU path: tensors must be on a ROCm device")
+
+
+def stream_ptr(device) -> int:
+    return torch.cuda.current_stream(device).cuda_stream
+
+
+def ptr(t):
+    """a tensor's device address for a pointer parameter; None stays None (NULL: the optional input or output is absent)"""
+    return None if t is None else t.data_ptr()
+
+
+def f32c(t):
+    """an upstream gradient as the kernels read it (f32, contiguous); None stays None"""
+    return None if t is None else t.to(torch.float32).contiguous()

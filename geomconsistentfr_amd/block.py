@@ -11,6 +11,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from ._lib import require_device as _require_device, stream_ptr as _stream_ptr
 
 
 @dataclass(frozen=True)
@@ -49,16 +50,6 @@ class RenderParams:
 
 
 _TABLE_CACHE = {}
-
-
-def _require_device(*tensors):
-    for t in tensors:
-        if t is not None and not t.is_cuda:
-            raise _lib.GcfrError("geomconsistentfr_amd has no CPU path: tensors must be on a ROCm device")
-
-
-def _stream_ptr(device) -> int:
-    return torch.cuda.current_stream(device).cuda_stream
 
 
 def sample_table(params: RenderParams, device) -> torch.Tensor:

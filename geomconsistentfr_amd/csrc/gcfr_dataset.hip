@@ -18,8 +18,9 @@
 //                      C1 = 0.01^2, C2 = 0.03^2 (dynamic range 1 for double images).  PARITY UNPINNED: MATLAB is not
 //                      available; this follows its documented defaults exactly as oracle/postprocess_statements.py does.
 //   Two passes over a workspace of 15 doubles per pixel (the five fields A, R, A^2, R^2, A R of three channels): rows,
-//   then columns + channels + the SSIM map + both masked sums (wave DPP reduction, one f64 atomic per workgroup and sum).
+//   then columns + channels + the SSIM map + both masked sums (gcfr_reduce.hpp's block sum, one f64 atomic per workgroup and sum).
 #include "gcfr_device.hpp"
+#include "gcfr_reduce.hpp"
 
 #include "../../include/gcfr.h"
 
@@ -59,13 +60,6 @@ struct MetricConsts {
     double k[kGaussTaps];  // normalised Gaussian, sigma 1.5
     double wc[3][3];       // the same filter along the channel axis (3 entries, replicate padding), folded: out[c] = sum wc[c][i] in[i]
 };
-
-__device__ inline double wave_sum_f64(double v)
-{
-    for (int off = 32; off > 0; off >>= 1)
-        v += __shfl_xor(v, off);
-    return v;
-}
 
 // pass 1: the five fields of the three channels, filtered along the ROWS axis (replicate padding) -> fields (B, P, 15)
 __global__ __launch_bounds__(256) void metrics_rows_kernel(const uint8_t *__restrict__ recon, const uint8_t *__restrict__ gt, int H, int W,
@@ -148,18 +142,10 @@ __global__ __launch_bounds__(256) void metrics_cols_kernel(const uint8_t *__rest
         part[2] = se;
         part[3] = m;
     }
-    __shared__ double s_part[4][4];
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const double s = wave_sum_f64(part[i]);
-        if (lane == 0)
-            s_part[wave][i] = s;
-    }
-    __syncthreads();
+    __shared__ BlockSum<4> red;
+    red.reduce(part);
     if (threadIdx.x < 4)
-        atomicAdd(sums + 4 * (size_t)b + threadIdx.x,
-                  (s_part[0][threadIdx.x] + s_part[1][threadIdx.x]) + (s_part[2][threadIdx.x] + s_part[3][threadIdx.x]));
+        atomicAdd(sums + 4 * (size_t)b + threadIdx.x, red.total(threadIdx.x));
 }
 
 __global__ void metrics_finish_kernel(const double *__restrict__ sums, int B, double *__restrict__ mse, double *__restrict__ dssim)

@@ -13,69 +13,28 @@
 //   g_final[l]  = (rgb[l,0] u[0] + rgb[l,1] u[1]) + rgb[l,2] u[2]      g_albedo[c] = g_rendered[c] shading_rgb[c] (recomputed)
 //   g_rgb[l,c] += sum_p final[l,p] u[c,p]                               in f64, as gcfr_render_bwd's grad_light_pt / grad_ambient
 //
-// Work split: a workgroup of 256 lanes owns chunks of kRigChunk = 1024 consecutive pixels of ONE face, four pixels per lane, and a
-// lane walks the L lights in order.  When H W is a multiple of four and every plane pointer is 16-byte aligned, a lane's four
-// pixels are consecutive and every plane is read and written with 16-byte accesses (all planes of all lights and channels keep
-// the alignment, their strides being multiples of H W); otherwise (an odd H W misaligns the second albedo plane and every second
-// light) lane t takes pixels t, t + 256, t + 512, t + 768 of the chunk with 4-byte accesses.  The face, hence the rig, is the same
-// for the whole workgroup: the 3 L rig values are read through wave-uniform addresses.
+// Work split: a workgroup of 256 lanes owns chunks of kRigChunk = 1024 consecutive pixels of ONE face, four pixels per lane
+// (gcfr_reduce.hpp: quad_load / quad_store), and a lane walks the L lights in order.  When H W is a multiple of four and every
+// plane pointer is 16-byte aligned, every plane is read and written with 16-byte accesses (all planes of all lights and channels
+// keep the alignment, their strides being multiples of H W); otherwise (an odd H W misaligns the second albedo plane and every
+// second light) with 4-byte accesses.  The face, hence the rig, is the same for the whole workgroup: the 3 L rig values are read
+// through wave-uniform addresses.
 // g_rgb: per light a lane adds its four products in f64, the wave reduces the three sums through an xor-shuffle tree, lane 0 adds
 // them (LDS f64 atomic) to the workgroup's accumulators, kRigLightTile lights at a time; a workgroup walks several chunks of its
 // face (the grid is capped near four workgroups per CU) and adds its accumulators to g_rgb with one global f64 atomic per entry at
 // the end (rigs longer than the tile: per chunk and tile).  The order of these f64 additions is the only freedom in the results.
 #include "gcfr_device.hpp"
+#include "gcfr_reduce.hpp"
 
 #include "../../include/gcfr.h"
 
 namespace gcfr {
 
-constexpr int kRigLanes = 256;
-constexpr int kRigChunk = 4 * kRigLanes;      // pixels per workgroup and step
+constexpr int kRigLanes = kQuadLanes;
+constexpr int kRigChunk = kQuadChunk;         // pixels per workgroup and step (gcfr_reduce.hpp: four per lane)
 constexpr int kRigLightTile = 1024;           // lights whose g_rgb partial sums a workgroup keeps in LDS (24 KiB)
 constexpr int kRigMaxLights = 4096;
 constexpr uint32_t kRigBwdGroups = 1024;      // the backward's grid is capped near this many workgroups (four per CU)
-
-// A lane's four pixels of a plane: VEC, pixels q .. q + 3 as one 16-byte access (H W % 4 == 0: all four in range or none);
-// otherwise pixels q, q + 256, q + 512, q + 768, each checked.  Pixels out of range read as 0 and are not written.
-template <bool VEC>
-__device__ inline void rig_load(const float *__restrict__ plane, uint32_t q, uint32_t HW, float (&v)[4])
-{
-    if (VEC) {
-        float4 t = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-        if (q < HW)
-            t = *reinterpret_cast<const float4 *>(plane + q);
-        v[0] = t.x, v[1] = t.y, v[2] = t.z, v[3] = t.w;
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const uint32_t p = q + (uint32_t)(k * kRigLanes);
-            v[k] = p < HW ? plane[p] : 0.0f;
-        }
-    }
-}
-
-template <bool VEC>
-__device__ inline void rig_store(float *__restrict__ plane, uint32_t q, uint32_t HW, const float (&v)[4])
-{
-    if (VEC) {
-        if (q < HW)
-            *reinterpret_cast<float4 *>(plane + q) = make_float4(v[0], v[1], v[2], v[3]);
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const uint32_t p = q + (uint32_t)(k * kRigLanes);
-            if (p < HW)
-                plane[p] = v[k];
-        }
-    }
-}
-
-__device__ inline double rig_wave_sum_f64(double v)
-{
-    for (int off = 32; off > 0; off >>= 1)
-        v += __shfl_xor(v, off);
-    return v;
-}
 
 template <bool VEC>
 __global__ __launch_bounds__(kRigLanes) void light_rig_fwd_kernel(
@@ -83,15 +42,15 @@ __global__ __launch_bounds__(kRigLanes) void light_rig_fwd_kernel(
     uint32_t L, uint32_t HW, uint32_t chunks, float *__restrict__ rendered, float *__restrict__ shading_rgb)
 {
     const uint32_t b = blockIdx.x / chunks, ch = blockIdx.x - b * chunks;          // (uniform)
-    const uint32_t q = ch * (uint32_t)kRigChunk + (VEC ? 4u * threadIdx.x : threadIdx.x);
+    const uint32_t q = quad_first<VEC>(ch * (uint32_t)kRigChunk);
     const float *rig = rgb + (size_t)b * rgb_stride;
     const float *fb = final_shading + (size_t)b * L * HW;
     const size_t plane3 = (size_t)b * 3u * HW;
     float al[3][4], f[4], acc[3][4];
 #pragma unroll
     for (int c = 0; c < 3; ++c)
-        rig_load<VEC>(albedo + plane3 + (size_t)c * HW, q, HW, al[c]);
-    rig_load<VEC>(fb, q, HW, f);
+        quad_load<VEC>(albedo + plane3 + (size_t)c * HW, q, HW, al[c]);
+    quad_load<VEC>(fb, q, HW, f);
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         const float r = rig[c];
@@ -101,7 +60,7 @@ __global__ __launch_bounds__(kRigLanes) void light_rig_fwd_kernel(
     }
 #pragma unroll 4
     for (uint32_t l = 1; l < L; ++l) {
-        rig_load<VEC>(fb + (size_t)l * HW, q, HW, f);
+        quad_load<VEC>(fb + (size_t)l * HW, q, HW, f);
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const float r = rig[3u * l + c];
@@ -113,11 +72,11 @@ __global__ __launch_bounds__(kRigLanes) void light_rig_fwd_kernel(
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         if (shading_rgb)
-            rig_store<VEC>(shading_rgb + plane3 + (size_t)c * HW, q, HW, acc[c]);
+            quad_store<VEC>(shading_rgb + plane3 + (size_t)c * HW, q, HW, acc[c]);
 #pragma unroll
         for (int k = 0; k < 4; ++k)
             al[c][k] = al[c][k] * acc[c][k];
-        rig_store<VEC>(rendered + plane3 + (size_t)c * HW, q, HW, al[c]);
+        quad_store<VEC>(rendered + plane3 + (size_t)c * HW, q, HW, al[c]);
     }
 }
 
@@ -152,17 +111,17 @@ __global__ __launch_bounds__(kRigLanes) void light_rig_bwd_kernel(
         __syncthreads();
     }
     for (uint32_t ch = j; ch < chunks; ch += groups) {                             // (uniform trip count: the barriers below are safe)
-        const uint32_t q = ch * (uint32_t)kRigChunk + (VEC ? 4u * tid : tid);
+        const uint32_t q = quad_first<VEC>(ch * (uint32_t)kRigChunk);
         float u[3][4], gr[3][4], sh[3][4], f[4];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const size_t off = plane3 + (size_t)c * HW;
             if (g_rendered) {
                 float al[4];
-                rig_load<VEC>(g_rendered + off, q, HW, gr[c]);
-                rig_load<VEC>(albedo + off, q, HW, al);
+                quad_load<VEC>(g_rendered + off, q, HW, gr[c]);
+                quad_load<VEC>(albedo + off, q, HW, al);
                 if (g_shading_rgb) {
-                    rig_load<VEC>(g_shading_rgb + off, q, HW, u[c]);
+                    quad_load<VEC>(g_shading_rgb + off, q, HW, u[c]);
 #pragma unroll
                     for (int k = 0; k < 4; ++k)
                         u[c][k] = u[c][k] + gr[c][k] * al[k];
@@ -172,7 +131,7 @@ __global__ __launch_bounds__(kRigLanes) void light_rig_bwd_kernel(
                         u[c][k] = gr[c][k] * al[k];
                 }
             } else {
-                rig_load<VEC>(g_shading_rgb + off, q, HW, u[c]);
+                quad_load<VEC>(g_shading_rgb + off, q, HW, u[c]);
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
                     gr[c][k] = 0.0f;
@@ -184,7 +143,7 @@ __global__ __launch_bounds__(kRigLanes) void light_rig_bwd_kernel(
         for (uint32_t t0 = 0; t0 < L; t0 += (uint32_t)kRigLightTile) {
             const uint32_t t1 = L - t0 < (uint32_t)kRigLightTile ? L : t0 + (uint32_t)kRigLightTile;
             for (uint32_t l = t0; l < t1; ++l) {
-                rig_load<VEC>(fb + (size_t)l * HW, q, HW, f);
+                quad_load<VEC>(fb + (size_t)l * HW, q, HW, f);
                 const float r0 = rig[3u * l], r1 = rig[3u * l + 1u], r2 = rig[3u * l + 2u];
                 const float r[3] = {r0, r1, r2};
                 if (want_sh) {
@@ -204,7 +163,7 @@ __global__ __launch_bounds__(kRigLanes) void light_rig_bwd_kernel(
                         g[k] = g[k] + r1 * u[1][k];
                         g[k] = g[k] + r2 * u[2][k];
                     }
-                    rig_store<VEC>(gfb + (size_t)l * HW, q, HW, g);
+                    quad_store<VEC>(gfb + (size_t)l * HW, q, HW, g);
                 }
                 if (grig) {
 #pragma unroll
@@ -213,7 +172,7 @@ __global__ __launch_bounds__(kRigLanes) void light_rig_bwd_kernel(
                         s += (double)f[1] * (double)u[c][1];
                         s += (double)f[2] * (double)u[c][2];
                         s += (double)f[3] * (double)u[c][3];
-                        s = rig_wave_sum_f64(s);
+                        s = wave_sum_f64(s);
                         if ((tid & 63u) == 0)
                             atomicAdd(&sAcc[3u * (l - t0) + (uint32_t)c], s);
                     }
@@ -232,7 +191,7 @@ __global__ __launch_bounds__(kRigLanes) void light_rig_bwd_kernel(
 #pragma unroll
                 for (int k = 0; k < 4; ++k)
                     ga[k] = gr[c][k] * sh[c][k];                                   // (no g_rendered: 0 * 0)
-                rig_store<VEC>(g_albedo + plane3 + (size_t)c * HW, q, HW, ga);
+                quad_store<VEC>(g_albedo + plane3 + (size_t)c * HW, q, HW, ga);
             }
         }
     }
@@ -251,7 +210,6 @@ inline bool rig_shape_ok(int32_t B, int32_t L, int32_t H, int32_t W, int32_t rgb
         return false;
     return (uint64_t)B * ((HW + kRigChunk - 1) / kRigChunk) <= 0x7fffffffull;      // one workgroup per face and chunk fits the grid
 }
-inline bool rig_aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
 
 }  // namespace gcfr
 
@@ -264,8 +222,7 @@ extern "C" int gcfr_light_rig_fwd(const float *final_shading, const float *albed
         return GCFR_ERR_INVALID_ARGUMENT;
     const uint32_t HW = (uint32_t)H * (uint32_t)W, chunks = (HW + kRigChunk - 1) / kRigChunk;
     const uint32_t stride = rgb_batch == 1 ? 0u : 3u * (uint32_t)L;
-    const bool vec = HW % 4u == 0 && rig_aligned16(final_shading) && rig_aligned16(albedo) && rig_aligned16(rendered) &&
-                     rig_aligned16(shading_rgb);
+    const bool vec = quad_vec_ok(HW, final_shading, albedo, rendered, shading_rgb);
     const dim3 grid((uint32_t)B * chunks), block(kRigLanes);
     hipStream_t st = (hipStream_t)stream;
     if (vec)
@@ -288,8 +245,7 @@ extern "C" int gcfr_light_rig_bwd(const float *final_shading, const float *albed
     const uint32_t stride = rgb_batch == 1 ? 0u : 3u * (uint32_t)L;
     uint32_t groups = (kRigBwdGroups + (uint32_t)B - 1) / (uint32_t)B;             // workgroups per face
     groups = groups > chunks ? chunks : groups;
-    const bool vec = HW % 4u == 0 && rig_aligned16(final_shading) && rig_aligned16(albedo) && rig_aligned16(g_rendered) &&
-                     rig_aligned16(g_shading_rgb) && rig_aligned16(g_final) && rig_aligned16(g_albedo);
+    const bool vec = quad_vec_ok(HW, final_shading, albedo, g_rendered, g_shading_rgb, g_final, g_albedo);
     const dim3 grid((uint32_t)B * groups), block(kRigLanes);
     hipStream_t st = (hipStream_t)stream;
     if (vec)

@@ -15,9 +15,9 @@
 // and per channel filters the five maps X, Y, XX, YY, XY down the columns into LDS (5 x 16 x 42) and along the rows into
 // registers: the five blurred maps never reach HBM.  The SSIM map exists at the pixels whose whole window lies inside the
 // image (5 <= r < H-5, 5 <= c < W-5: the (H-10) x (W-10) 'valid' positions, indexed here by their CENTRE pixel).  Each lane adds
-// its map values, squared differences and mask values in f64; the workgroup reduces them in a fixed order (xor-shuffle tree,
-// then the four waves) into five doubles of the caller's workspace.  Two small kernels add the tiles of each image and then the
-// images, again in a fixed order: no floating-point atomic anywhere, so two calls on the same inputs give the same bits.
+// its map values, squared differences and mask values in f64; the workgroup reduces them with the fixed-order block sum
+// (gcfr_reduce.hpp, BlockSum) into five doubles of the caller's workspace.  Two small kernels add the tiles of each image and then
+// the images, again in a fixed order: no floating-point atomic anywhere, so two calls on the same inputs give the same bits.
 // LDS: 2 x 3 x 1099 + 5 x 672 floats = 39.8 KB -> three workgroups per CU.  The planes' stride is 26 * 42 + 7 = 1099 floats
 // (1099 mod 32 = 11): when the interleaved (NHWC) photograph is staged, consecutive lanes write channels 0, 1, 2 of one pixel
 // into three planes, and with the unpadded stride (1092 mod 32 = 4) the three groups of ~11 consecutive banks would overlap.
@@ -32,6 +32,7 @@
 // once per pixel: no atomics, bit-reproducible.  LDS 2 x 1872 + 5 x 1352 + 3 x 1092 floats = 55.1 KB -> two workgroups
 // (sixteen waves) per CU.
 #include "gcfr_device.hpp"
+#include "gcfr_reduce.hpp"
 
 #include "../../include/gcfr.h"
 
@@ -53,11 +54,63 @@ __device__ inline size_t photo_index(int layout, int b, int ch, int r, int c, in
     return layout == 0 ? (((size_t)b * H + r) * W + c) * 3 + ch : (((size_t)b * 3 + ch) * H + r) * W + c;
 }
 
-__device__ inline double wave_sum_f64_fixed(double v)
+// T8:619 / 641: the mask paste, bit-equal to the torch expression
+__device__ inline float paste(float rv, float m, float y)
 {
-    for (int off = 32; off > 0; off >>= 1)
-        v += __shfl_xor(v, off);
-    return v;
+    const float t1 = rv * m;
+    const float om = 1.0f - m;
+    const float t3 = om * y;
+    return t1 + t3;
+}
+
+// The SSIM arithmetic, stated once for the forward and for the backward's recomputation: the gradient belongs to its forward only
+// while both run these very operations.  Every accumulator starts at 0.0f and adds w[t] * v, tap 0 to tap 10.
+//
+// Along H: the five maps X, Y, XX, YY, XY of the staged planes pX, pY (row stride ROW_W) at N consecutive positions, into the five
+// planes of N floats of sMid.
+template <int ROW_W, int N, int LANES>
+__device__ inline void ssim_blur_columns(const float *pX, const float *pY, const LossWindow &win, float *sMid)
+{
+    for (int i = threadIdx.x; i < N; i += LANES) {
+        float ax = 0.0f, ay = 0.0f, axx = 0.0f, ayy = 0.0f, axy = 0.0f;
+#pragma unroll
+        for (int t = 0; t < kWin; ++t) {
+            const float x = pX[i + t * ROW_W], y = pY[i + t * ROW_W], w = win.w[t];
+            ax += w * x;
+            ay += w * y;
+            axx += w * (x * x);
+            ayy += w * (y * y);
+            axy += w * (x * y);
+        }
+        sMid[0 * N + i] = ax;
+        sMid[1 * N + i] = ay;
+        sMid[2 * N + i] = axx;
+        sMid[3 * N + i] = ayy;
+        sMid[4 * N + i] = axy;
+    }
+}
+
+// Along W at one map position (p = its first tap in plane 0 of sMid, planes N floats apart), then the two factors of the map:
+// lum = (2 mu1 mu2 + C1) / B1, cs = (2 s12 + C2) / B2.
+struct SsimPoint {
+    float mu1, mu2, B1, B2, lum, cs;
+};
+template <int N>
+__device__ inline SsimPoint ssim_point(const float *p, const LossWindow &win, float C1, float C2)
+{
+    float mu1 = 0.0f, mu2 = 0.0f, xx = 0.0f, yy = 0.0f, xy = 0.0f;
+#pragma unroll
+    for (int t = 0; t < kWin; ++t) {
+        const float w = win.w[t];
+        mu1 += w * p[0 * N + t];
+        mu2 += w * p[1 * N + t];
+        xx += w * p[2 * N + t];
+        yy += w * p[3 * N + t];
+        xy += w * p[4 * N + t];
+    }
+    const float s1 = xx - mu1 * mu1, s2 = yy - mu2 * mu2, s12 = xy - mu1 * mu2;
+    const float B1 = mu1 * mu1 + mu2 * mu2 + C1, B2 = s1 + s2 + C2;
+    return {mu1, mu2, B1, B2, (2.0f * mu1 * mu2 + C1) / B1, (2.0f * s12 + C2) / B2};
 }
 
 __global__ __launch_bounds__(256) void image_losses_fwd_kernel(const float *__restrict__ rendered, const float *__restrict__ img,
@@ -67,7 +120,7 @@ __global__ __launch_bounds__(256) void image_losses_fwd_kernel(const float *__re
 {
     __shared__ float sX[3 * kFwdPlane], sY[3 * kFwdPlane];
     __shared__ float sMid[5 * kLossTileH * kFwdW];
-    __shared__ double sRed[4][kLossPartials];
+    __shared__ BlockSum<kLossPartials> red;
     const int b = blockIdx.y, tile = blockIdx.x, tid = threadIdx.x;
     const int r0 = (tile / tiles_x) * kLossTileH, c0 = (tile % tiles_x) * kLossTileW;
     constexpr int kItems = 3 * kFwdH * kFwdW;
@@ -107,13 +160,10 @@ __global__ __launch_bounds__(256) void image_losses_fwd_kernel(const float *__re
             const float rv = rendered[q];
             const float m = mask ? mask[((size_t)b * H + r) * W + c] : 1.0f;
             const float y = sY[ch * kFwdPlane + k];
-            const float t1 = rv * m;
-            const float om = 1.0f - m;
-            const float t3 = om * y;
-            x = t1 + t3;                                                       // T8:619 / 641
+            x = paste(rv, m, y);
             if (rr >= kWinR && rr < kWinR + kLossTileH && cc >= kWinR && cc < kWinR + kLossTileW) {
                 composite[q] = x;
-                const float d = t1 - y * m;                                   // T8:633
+                const float d = rv * m - y * m;                               // T8:633
                 acc_sq += (double)(d * d);
                 acc_m += (double)m;
             }
@@ -126,67 +176,30 @@ __global__ __launch_bounds__(256) void image_losses_fwd_kernel(const float *__re
     constexpr int kMid = kLossTileH * kFwdW;
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
-        const float *pX = sX + ch * kFwdPlane, *pY = sY + ch * kFwdPlane;
-        for (int i = tid; i < kMid; i += 256) {                                // along H
-            float ax = 0.0f, ay = 0.0f, axx = 0.0f, ayy = 0.0f, axy = 0.0f;
-#pragma unroll
-            for (int t = 0; t < kWin; ++t) {
-                const float x = pX[i + t * kFwdW], y = pY[i + t * kFwdW], w = win.w[t];
-                ax += w * x;
-                ay += w * y;
-                axx += w * (x * x);
-                ayy += w * (y * y);
-                axy += w * (x * y);
-            }
-            sMid[0 * kMid + i] = ax;
-            sMid[1 * kMid + i] = ay;
-            sMid[2 * kMid + i] = axx;
-            sMid[3 * kMid + i] = ayy;
-            sMid[4 * kMid + i] = axy;
-        }
+        ssim_blur_columns<kFwdW, kMid, 256>(sX + ch * kFwdPlane, sY + ch * kFwdPlane, win, sMid);
         __syncthreads();
         for (int i = tid; i < kLossTileH * kLossTileW; i += 256) {            // along W, then the map
             const int r = i / kLossTileW, c = i - r * kLossTileW;
             const int pr = r0 + r, pc = c0 + c;
             if (pr >= kWinR && pr < H - kWinR && pc >= kWinR && pc < W - kWinR) {
-                const float *p = sMid + r * kFwdW + c;
-                float mu1 = 0.0f, mu2 = 0.0f, xx = 0.0f, yy = 0.0f, xy = 0.0f;
-#pragma unroll
-                for (int t = 0; t < kWin; ++t) {
-                    const float w = win.w[t];
-                    mu1 += w * p[0 * kMid + t];
-                    mu2 += w * p[1 * kMid + t];
-                    xx += w * p[2 * kMid + t];
-                    yy += w * p[3 * kMid + t];
-                    xy += w * p[4 * kMid + t];
-                }
-                const float s1 = xx - mu1 * mu1, s2 = yy - mu2 * mu2, s12 = xy - mu1 * mu2;
-                const float cs = (2.0f * s12 + C2) / (s1 + s2 + C2);
-                const float lum = (2.0f * mu1 * mu2 + C1) / (mu1 * mu1 + mu2 * mu2 + C1);
-                acc_s[ch] += (double)(lum * cs);
+                const SsimPoint s = ssim_point<kMid>(sMid + r * kFwdW + c, win, C1, C2);
+                acc_s[ch] += (double)(s.lum * s.cs);
             }
         }
         __syncthreads();
     }
 
     const double vals[kLossPartials] = {acc_s[0], acc_s[1], acc_s[2], acc_sq, acc_m};
-    const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int k = 0; k < kLossPartials; ++k) {
-        const double s = wave_sum_f64_fixed(vals[k]);
-        if (lane == 0)
-            sRed[wave][k] = s;
-    }
-    __syncthreads();
+    red.reduce(vals);
     if (tid < kLossPartials)
-        partials[((size_t)b * gridDim.x + tile) * kLossPartials + tid] = (sRed[0][tid] + sRed[1][tid]) + (sRed[2][tid] + sRed[3][tid]);
+        partials[((size_t)b * gridDim.x + tile) * kLossPartials + tid] = red.total(tid);
 }
 
-// the tiles of one image, lane t taking tiles t, t + 256, ... in order, then the same tree as above
+// the tiles of one image, lane t taking tiles t, t + 256, ... in order, then the same block sum
 __global__ __launch_bounds__(256) void image_losses_finish_image_kernel(const double *__restrict__ partials, int tiles, double n_valid,
                                                                         float *__restrict__ ssim_out, double *__restrict__ per_image)
 {
-    __shared__ double sRed[4][kLossPartials];
+    __shared__ BlockSum<kLossPartials> red;
     const int b = blockIdx.x, tid = threadIdx.x;
     double acc[kLossPartials] = {0.0, 0.0, 0.0, 0.0, 0.0};
     for (int t = tid; t < tiles; t += 256) {
@@ -195,16 +208,9 @@ __global__ __launch_bounds__(256) void image_losses_finish_image_kernel(const do
         for (int k = 0; k < kLossPartials; ++k)
             acc[k] += p[k];
     }
-    const int lane = tid & 63, wave = tid >> 6;
-#pragma unroll
-    for (int k = 0; k < kLossPartials; ++k) {
-        const double s = wave_sum_f64_fixed(acc[k]);
-        if (lane == 0)
-            sRed[wave][k] = s;
-    }
-    __syncthreads();
+    red.reduce(acc);
     if (tid < kLossPartials) {
-        const double s = (sRed[0][tid] + sRed[1][tid]) + (sRed[2][tid] + sRed[3][tid]);
+        const double s = red.total(tid);
         if (tid < 3)
             ssim_out[3 * (size_t)b + tid] = (float)(s / n_valid);
         else
@@ -220,8 +226,8 @@ __global__ __launch_bounds__(64) void image_losses_finish_batch_kernel(const dou
         sq += per_image[2 * (size_t)b];
         m += per_image[2 * (size_t)b + 1];
     }
-    sq = wave_sum_f64_fixed(sq);
-    m = wave_sum_f64_fixed(m);
+    sq = wave_sum_f64(sq);
+    m = wave_sum_f64(m);
     if (threadIdx.x == 0) {
         sums[0] = sq;
         sums[1] = m;
@@ -263,57 +269,24 @@ __global__ __launch_bounds__(512) void image_losses_bwd_kernel(const float *__re
                     y = img[photo_index(layout, b, ch, r, c, H, W)];
                     const float rv = rendered[(((size_t)b * 3 + ch) * H + r) * W + c];
                     const float m = mask ? mask[((size_t)b * H + r) * W + c] : 1.0f;
-                    const float t1 = rv * m;
-                    const float om = 1.0f - m;
-                    const float t3 = om * y;
-                    x = t1 + t3;
+                    x = paste(rv, m, y);
                 }
                 sX[i] = x;
                 sY[i] = y;
             }
             __syncthreads();
-            for (int i = tid; i < kMid; i += 512) {                            // along H: map rows r0-5 ..., all 52 columns
-                float ax = 0.0f, ay = 0.0f, axx = 0.0f, ayy = 0.0f, axy = 0.0f;
-#pragma unroll
-                for (int t = 0; t < kWin; ++t) {
-                    const float x = sX[i + t * kBwdW], y = sY[i + t * kBwdW], w = win.w[t];
-                    ax += w * x;
-                    ay += w * y;
-                    axx += w * (x * x);
-                    ayy += w * (y * y);
-                    axy += w * (x * y);
-                }
-                sMid[0 * kMid + i] = ax;
-                sMid[1 * kMid + i] = ay;
-                sMid[2 * kMid + i] = axx;
-                sMid[3 * kMid + i] = ayy;
-                sMid[4 * kMid + i] = axy;
-            }
+            ssim_blur_columns<kBwdW, kMid, 512>(sX, sY, win, sMid);            // map rows r0-5 ..., all 52 columns
             __syncthreads();
             for (int i = tid; i < kMap; i += 512) {                            // along W, then the map's adjoints
                 const int mr = i / kMapW, mc = i - mr * kMapW;
                 const int qr = r0 - kWinR + mr, qc = c0 - kWinR + mc;          // the map position's centre pixel
                 float a = 0.0f, bb = 0.0f, c_ = 0.0f;
                 if (qr >= kWinR && qr < H - kWinR && qc >= kWinR && qc < W - kWinR) {
-                    const float *p = sMid + mr * kBwdW + mc;
-                    float mu1 = 0.0f, mu2 = 0.0f, xx = 0.0f, yy = 0.0f, xy = 0.0f;
-#pragma unroll
-                    for (int t = 0; t < kWin; ++t) {
-                        const float w = win.w[t];
-                        mu1 += w * p[0 * kMid + t];
-                        mu2 += w * p[1 * kMid + t];
-                        xx += w * p[2 * kMid + t];
-                        yy += w * p[3 * kMid + t];
-                        xy += w * p[4 * kMid + t];
-                    }
-                    const float s1 = xx - mu1 * mu1, s2 = yy - mu2 * mu2, s12 = xy - mu1 * mu2;
-                    const float B1 = mu1 * mu1 + mu2 * mu2 + C1, B2 = s1 + s2 + C2;
-                    const float lum = (2.0f * mu1 * mu2 + C1) / B1;
-                    const float cs = (2.0f * s12 + C2) / B2;
+                    const SsimPoint s = ssim_point<kMid>(sMid + mr * kBwdW + mc, win, C1, C2);
                     // d map / d blur(X), d blur(XX), d blur(XY)
-                    const float d_mu1 = 2.0f * cs * (mu2 - lum * mu1) / B1 + 2.0f * lum * (cs * mu1 - mu2) / B2;
-                    const float d_xx = -(lum * cs) / B2;
-                    const float d_xy = 2.0f * lum / B2;
+                    const float d_mu1 = 2.0f * s.cs * (s.mu2 - s.lum * s.mu1) / s.B1 + 2.0f * s.lum * (s.cs * s.mu1 - s.mu2) / s.B2;
+                    const float d_xx = -(s.lum * s.cs) / s.B2;
+                    const float d_xy = 2.0f * s.lum / s.B2;
                     a = u * d_mu1;
                     bb = u * d_xx;
                     c_ = u * d_xy;

@@ -14,15 +14,15 @@
 // -ffp-contract=off), in the order of the torch expressions: the two products, their difference, its absolute value.  The grey
 // value is ((a0 + a1) + a2) * (1.0f / 3.0f), the order and the reciprocal factor of ATen's mean over a dimension of three.
 //
-// Forward: a workgroup of 256 lanes owns kSupChunk = 1024 consecutive pixels of the flat (B H W) range, four per lane.  When
-// H W is a multiple of four and every plane is 16-byte aligned, a lane loads its four consecutive pixels as one float4 per plane
-// (eight loads in flight); otherwise (the three albedo planes of an image start H W floats apart, so they lose their alignment)
-// lane t takes pixels t, t + 256, t + 512, t + 768 of the chunk with scalar loads.  In the vector path B H W is a multiple of
-// four, so no vector straddles the end.  A lane adds |depth m - gt m|, m, |grey mf - a mf| and mf in f64; the logits are spread
-// over the whole grid (element i belongs to global lane i mod lanes) and their softplus is evaluated and added in f64.  The
-// workgroup reduces the five sums through a fixed xor-shuffle tree and its four waves in a fixed order into five doubles of the
-// caller's workspace.  The finishing launch (one workgroup) adds the workgroups' partials and the per-image ambient and lighting
-// addends in a fixed order and evaluates the five scalar formulas in f32.  No floating-point atomics: two calls return the same bits.
+// Forward: a workgroup of 256 lanes owns kSupChunk = 1024 consecutive pixels of the flat (B H W) range, four per lane, through
+// the four-pixel access of gcfr_reduce.hpp: one float4 per plane when H W is a multiple of four and every plane is 16-byte
+// aligned (eight loads in flight; B H W is then a multiple of four, so no vector straddles the end), otherwise (the three albedo
+// planes of an image start H W floats apart, so they lose their alignment) pixels t, t + 256, t + 512, t + 768 with 4-byte loads.
+// A lane adds |depth m - gt m|, m, |grey mf - a mf| and mf of its pixels, in ascending order, in f64; the logits are spread over the
+// whole grid (element i belongs to global lane i mod lanes) and their softplus is evaluated and added in f64.  The workgroup
+// reduces the five sums with the fixed-order block sum (gcfr_reduce.hpp, BlockSum) into five doubles of the caller's workspace.
+// The finishing launch (one workgroup) adds the workgroups' partials and the per-image ambient and lighting addends the same way
+// and evaluates the five scalar formulas in f32.  No floating-point atomics: two calls return the same bits.
 //
 // Backward: the same chunks; every gradient element is written once by one lane.  The five upstream gradients and the two mask
 // sums are read from device memory (no host synchronisation).  The small outputs (grad_unit_light, grad_ambient_values,
@@ -30,23 +30,17 @@
 // built from separately rounded f32 operations only, so that the f32 restatement (tests/supervised_losses_emulation.py) returns
 // the same bits.
 #include "gcfr_device.hpp"
+#include "gcfr_reduce.hpp"
 
 #include "../../include/gcfr.h"
 
 namespace gcfr {
 
-constexpr int kSupLanes = 256;
-constexpr int kSupChunk = 4 * kSupLanes;      // pixels per workgroup
+constexpr int kSupLanes = kQuadLanes;
+constexpr int kSupChunk = kQuadChunk;         // pixels per workgroup (gcfr_reduce.hpp: four per lane)
 constexpr int kSupPartials = 5;               // per workgroup: S_depth, M, S_albedo, M_fill, S_softplus
 constexpr int kSupFinish = 7;                 // + the ambient and lighting sums of the finishing launch
 constexpr float kThird = 1.0f / 3.0f;
-
-__device__ inline double sup_wave_sum_f64(double v)
-{
-    for (int off = 32; off > 0; off >>= 1)
-        v += __shfl_xor(v, off);
-    return v;
-}
 
 // sign(0) = 0, as l1_loss's backward has it; NaN gives 0
 __device__ inline float sup_sgn(float d) { return d > 0.0f ? 1.0f : (d < 0.0f ? -1.0f : 0.0f); }
@@ -80,44 +74,84 @@ __device__ inline void sup_pixel_fwd(float d, float g, float m, float a0, float 
     acc[3] += (double)mf;
 }
 
+// The albedo planes of a lane's four pixels.  Pixel p = b H W + hw of the flat (B H W) range has its channel c at
+// albedo[p + (2 b + c) H W].  VEC: the four pixels lie in one image (H W % 4 == 0); otherwise each may lie in another one.
+template <bool VEC>
+struct SupAlbedoQuad {
+    uint32_t q, HW, N;
+    size_t shift[VEC ? 1 : 4];                                         // 2 b H W, per pixel
+
+    __device__ SupAlbedoQuad(uint32_t q_, uint32_t HW_, uint32_t N_) : q(q_), HW(HW_), N(N_)
+    {
+#pragma unroll
+        for (int k = 0; k < (VEC ? 1 : 4); ++k) {
+            const uint32_t p = quad_pixel<VEC>(q, k);
+            shift[k] = p < N ? 2u * (size_t)(p / HW) * HW : 0u;
+        }
+    }
+    __device__ void load(const float *__restrict__ albedo, int c, float (&v)[4]) const
+    {
+        if constexpr (VEC) {
+            quad_load<true>(albedo + shift[0] + (size_t)c * HW, q, N, v);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const uint32_t p = quad_pixel<false>(q, k);
+                v[k] = p < N ? albedo[shift[k] + (size_t)c * HW + p] : 0.0f;
+            }
+        }
+    }
+    __device__ void store(float *__restrict__ grad, int c, const float (&v)[4]) const
+    {
+        if constexpr (VEC) {
+            quad_store<true>(grad + shift[0] + (size_t)c * HW, q, N, v);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const uint32_t p = quad_pixel<false>(q, k);
+                if (p < N)
+                    grad[shift[k] + (size_t)c * HW + p] = v[k];
+            }
+        }
+    }
+};
+
+// the four pixels of a lane, added into acc in ascending order
+template <bool VEC>
+__device__ inline void sup_quad_fwd(const float *__restrict__ depth, const float *__restrict__ gt_depth, const float *__restrict__ mask,
+                                    const float *__restrict__ albedo, const float *__restrict__ gt_albedo,
+                                    const float *__restrict__ mask_fill, uint32_t HW, uint32_t N, double (&acc)[4])
+{
+    const uint32_t q = quad_first<VEC>(blockIdx.x * (uint32_t)kSupChunk);  // (N < 2^31: the chunk's last pixel fits)
+    if (q < N) {                                                       // (the lane's first pixel; under it the vector accesses need
+        const SupAlbedoQuad<VEC> alb(q, HW, N);                        //  no test of their own: eight loads in flight)
+        float d[4], g[4], m[4], a[3][4], ga[4], mf[4];
+        quad_load<VEC>(depth, q, N, d);
+        quad_load<VEC>(gt_depth, q, N, g);
+        quad_load<VEC>(mask, q, N, m);
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            alb.load(albedo, c, a[c]);
+        quad_load<VEC>(gt_albedo, q, N, ga);
+        quad_load<VEC>(mask_fill, q, N, mf);
+#pragma unroll
+        for (int k = 0; k < 4; ++k)                                    // (a pixel past the end reads as zeros and adds +0.0: no change)
+            sup_pixel_fwd(d[k], g[k], m[k], a[0][k], a[1][k], a[2][k], ga[k], mf[k], acc);
+    }
+}
+
 __global__ __launch_bounds__(kSupLanes) void supervised_losses_fwd_kernel(
     const float *__restrict__ depth, const float *__restrict__ gt_depth, const float *__restrict__ mask,
     const float *__restrict__ albedo, const float *__restrict__ gt_albedo, const float *__restrict__ mask_fill,
     const float *__restrict__ logits, uint32_t n_logits, uint32_t HW, uint32_t N, int vec, double *__restrict__ partials)
 {
-    __shared__ double sRed[4][kSupPartials];
+    __shared__ BlockSum<kSupPartials> red;
     const uint32_t tid = threadIdx.x;
-    const uint32_t p0 = blockIdx.x * (uint32_t)kSupChunk;              // (N < 2^31: p0 + 1023 fits)
     double acc[4] = {0.0, 0.0, 0.0, 0.0};
-    if (vec) {                                                         // (uniform) HW % 4 == 0, hence N % 4 == 0
-        const uint32_t p = p0 + 4u * tid;
-        if (p < N) {
-            const uint32_t b = p / HW, hw = p - b * HW;
-            const float *pa = albedo + ((size_t)b * 3u) * HW + hw;
-            const float4 d = *reinterpret_cast<const float4 *>(depth + p);
-            const float4 g = *reinterpret_cast<const float4 *>(gt_depth + p);
-            const float4 m = *reinterpret_cast<const float4 *>(mask + p);
-            const float4 a0 = *reinterpret_cast<const float4 *>(pa);
-            const float4 a1 = *reinterpret_cast<const float4 *>(pa + HW);
-            const float4 a2 = *reinterpret_cast<const float4 *>(pa + 2 * (size_t)HW);
-            const float4 ga = *reinterpret_cast<const float4 *>(gt_albedo + p);
-            const float4 mf = *reinterpret_cast<const float4 *>(mask_fill + p);
-            sup_pixel_fwd(d.x, g.x, m.x, a0.x, a1.x, a2.x, ga.x, mf.x, acc);
-            sup_pixel_fwd(d.y, g.y, m.y, a0.y, a1.y, a2.y, ga.y, mf.y, acc);
-            sup_pixel_fwd(d.z, g.z, m.z, a0.z, a1.z, a2.z, ga.z, mf.z, acc);
-            sup_pixel_fwd(d.w, g.w, m.w, a0.w, a1.w, a2.w, ga.w, mf.w, acc);
-        }
-    } else {
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const uint32_t p = p0 + tid + (uint32_t)(k * kSupLanes);
-            if (p < N) {
-                const uint32_t b = p / HW, hw = p - b * HW;
-                const float *pa = albedo + ((size_t)b * 3u) * HW + hw;
-                sup_pixel_fwd(depth[p], gt_depth[p], mask[p], pa[0], pa[HW], pa[2 * (size_t)HW], gt_albedo[p], mask_fill[p], acc);
-            }
-        }
-    }
+    if (vec)                                                           // (uniform)
+        sup_quad_fwd<true>(depth, gt_depth, mask, albedo, gt_albedo, mask_fill, HW, N, acc);
+    else
+        sup_quad_fwd<false>(depth, gt_depth, mask, albedo, gt_albedo, mask_fill, HW, N, acc);
     double acc_g = 0.0;
     if (logits) {                                                      // (uniform) T8:642: -log sigmoid(x) = max(-x, 0) + log1p(e^-|x|)
         const uint32_t stride = gridDim.x * (uint32_t)kSupLanes;       // (grid <= 2^21 workgroups: fits)
@@ -127,25 +161,18 @@ __global__ __launch_bounds__(kSupLanes) void supervised_losses_fwd_kernel(
         }
     }
     const double vals[kSupPartials] = {acc[0], acc[1], acc[2], acc[3], acc_g};
-    const uint32_t lane = tid & 63u, wave = tid >> 6;
-#pragma unroll
-    for (int k = 0; k < kSupPartials; ++k) {
-        const double s = sup_wave_sum_f64(vals[k]);
-        if (lane == 0)
-            sRed[wave][k] = s;
-    }
-    __syncthreads();
+    red.reduce(vals);
     if (tid < (uint32_t)kSupPartials)
-        partials[(size_t)blockIdx.x * kSupPartials + tid] = (sRed[0][tid] + sRed[1][tid]) + (sRed[2][tid] + sRed[3][tid]);
+        partials[(size_t)blockIdx.x * kSupPartials + tid] = red.total(tid);
 }
 
 // one workgroup: the workgroups' partials (lane t takes t, t + 256, ...), the images' ambient and lighting addends (likewise), the
-// same tree as above, then the five scalar formulas in f32
+// same block sum, then the five scalar formulas in f32
 __global__ __launch_bounds__(kSupLanes) void supervised_losses_finish_kernel(
     const double *__restrict__ partials, uint32_t n_groups, const float *__restrict__ unit_light, const float *__restrict__ ambient,
     const float *__restrict__ lightings, uint32_t B, uint32_t n_logits, float *__restrict__ terms, double *__restrict__ sums)
 {
-    __shared__ double sRed[4][kSupFinish];
+    __shared__ BlockSum<kSupFinish> red;
     const uint32_t tid = threadIdx.x;
     double acc[kSupFinish] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
     for (uint32_t t = tid; t < n_groups; t += kSupLanes) {
@@ -160,19 +187,12 @@ __global__ __launch_bounds__(kSupLanes) void supervised_losses_finish_kernel(
         const float dot = (u[0] * l[1] + u[1] * l[2]) + u[2] * l[3];   // T8:636
         acc[6] += (double)(1.0f - dot);
     }
-    const uint32_t lane = tid & 63u, wave = tid >> 6;
-#pragma unroll
-    for (int k = 0; k < kSupFinish; ++k) {
-        const double s = sup_wave_sum_f64(acc[k]);
-        if (lane == 0)
-            sRed[wave][k] = s;
-    }
-    __syncthreads();
+    red.reduce(acc);
     if (tid == 0) {
         double r[kSupFinish];
 #pragma unroll
         for (int k = 0; k < kSupFinish; ++k)
-            r[k] = (sRed[0][k] + sRed[1][k]) + (sRed[2][k] + sRed[3][k]);
+            r[k] = red.total(k);
         const float fB = (float)B;
         terms[0] = (float)r[0] / (float)r[1];                          // 0 / 0 = NaN for an all-zero mask, as torch
         terms[1] = 2.5f * ((float)r[5] / fB);
@@ -209,63 +229,51 @@ __device__ inline float sup_pixel_bwd_albedo(float a0, float a1, float a2, float
     return ((sa * sup_sgn(xm - ym)) * mf) * kThird;
 }
 
-__global__ __launch_bounds__(kSupLanes) void supervised_losses_bwd_kernel(SupBwdArgs a)
+// grad_depth and grad_albedo at the four pixels of a lane
+template <bool VEC>
+__device__ inline void sup_quad_bwd(const SupBwdArgs &a)
 {
-    const uint32_t tid = threadIdx.x, HW = a.HW, N = a.N;
-    const uint32_t p0 = blockIdx.x * (uint32_t)kSupChunk;
+    const uint32_t N = a.N, q = quad_first<VEC>(blockIdx.x * (uint32_t)kSupChunk);
     const bool do_d = a.g_depth != nullptr, do_a = a.g_albedo != nullptr;         // (uniform)
     const float sd = do_d ? a.g_depth[0] / (float)a.sums[1] : 0.0f;
     const float sa = do_a ? (a.g_albedo[0] * 5.0f) / (float)a.sums[3] : 0.0f;
-    if (a.vec) {
-        const uint32_t p = p0 + 4u * tid;
-        if (p < N) {
-            const uint32_t b = p / HW, hw = p - b * HW;
-            const size_t qa = ((size_t)b * 3u) * HW + hw;
-            float4 od = make_float4(0.0f, 0.0f, 0.0f, 0.0f), oa = od;
-            if (do_d) {
-                const float4 d = *reinterpret_cast<const float4 *>(a.depth + p);
-                const float4 g = *reinterpret_cast<const float4 *>(a.gt_depth + p);
-                const float4 m = *reinterpret_cast<const float4 *>(a.mask + p);
-                od = make_float4(sup_pixel_bwd_depth(d.x, g.x, m.x, sd), sup_pixel_bwd_depth(d.y, g.y, m.y, sd),
-                                 sup_pixel_bwd_depth(d.z, g.z, m.z, sd), sup_pixel_bwd_depth(d.w, g.w, m.w, sd));
-            }
-            if (do_a) {
-                const float *pa = a.albedo + qa;
-                const float4 a0 = *reinterpret_cast<const float4 *>(pa);
-                const float4 a1 = *reinterpret_cast<const float4 *>(pa + HW);
-                const float4 a2 = *reinterpret_cast<const float4 *>(pa + 2 * (size_t)HW);
-                const float4 ga = *reinterpret_cast<const float4 *>(a.gt_albedo + p);
-                const float4 mf = *reinterpret_cast<const float4 *>(a.mask_fill + p);
-                oa = make_float4(sup_pixel_bwd_albedo(a0.x, a1.x, a2.x, ga.x, mf.x, sa), sup_pixel_bwd_albedo(a0.y, a1.y, a2.y, ga.y, mf.y, sa),
-                                 sup_pixel_bwd_albedo(a0.z, a1.z, a2.z, ga.z, mf.z, sa), sup_pixel_bwd_albedo(a0.w, a1.w, a2.w, ga.w, mf.w, sa));
-            }
-            *reinterpret_cast<float4 *>(a.grad_depth + p) = od;
-            float *po = a.grad_albedo + qa;
-            *reinterpret_cast<float4 *>(po) = oa;
-            *reinterpret_cast<float4 *>(po + HW) = oa;
-            *reinterpret_cast<float4 *>(po + 2 * (size_t)HW) = oa;
-        }
-    } else {
+    if (q < N) {                                                                  // (as in the forward)
+        const SupAlbedoQuad<VEC> alb(q, a.HW, N);
+        float od[4] = {0.0f, 0.0f, 0.0f, 0.0f}, oa[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+        if (do_d) {
+            float d[4], g[4], m[4];
+            quad_load<VEC>(a.depth, q, N, d);
+            quad_load<VEC>(a.gt_depth, q, N, g);
+            quad_load<VEC>(a.mask, q, N, m);
 #pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            const uint32_t p = p0 + tid + (uint32_t)(k * kSupLanes);
-            if (p < N) {
-                const uint32_t b = p / HW, hw = p - b * HW;
-                const size_t qa = ((size_t)b * 3u) * HW + hw;
-                const float od = do_d ? sup_pixel_bwd_depth(a.depth[p], a.gt_depth[p], a.mask[p], sd) : 0.0f;
-                float oa = 0.0f;
-                if (do_a) {
-                    const float *pa = a.albedo + qa;
-                    oa = sup_pixel_bwd_albedo(pa[0], pa[HW], pa[2 * (size_t)HW], a.gt_albedo[p], a.mask_fill[p], sa);
-                }
-                a.grad_depth[p] = od;
-                float *po = a.grad_albedo + qa;
-                po[0] = oa;
-                po[HW] = oa;
-                po[2 * (size_t)HW] = oa;
-            }
+            for (int k = 0; k < 4; ++k)
+                od[k] = sup_pixel_bwd_depth(d[k], g[k], m[k], sd);
         }
+        if (do_a) {
+            float c[3][4], ga[4], mf[4];
+#pragma unroll
+            for (int ch = 0; ch < 3; ++ch)
+                alb.load(a.albedo, ch, c[ch]);
+            quad_load<VEC>(a.gt_albedo, q, N, ga);
+            quad_load<VEC>(a.mask_fill, q, N, mf);
+#pragma unroll
+            for (int k = 0; k < 4; ++k)
+                oa[k] = sup_pixel_bwd_albedo(c[0][k], c[1][k], c[2][k], ga[k], mf[k], sa);
+        }
+        quad_store<VEC>(a.grad_depth, q, N, od);
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch)
+            alb.store(a.grad_albedo, ch, oa);
     }
+}
+
+__global__ __launch_bounds__(kSupLanes) void supervised_losses_bwd_kernel(SupBwdArgs a)
+{
+    const uint32_t tid = threadIdx.x;
+    if (a.vec)                                                                    // (uniform)
+        sup_quad_bwd<true>(a);
+    else
+        sup_quad_bwd<false>(a);
     // the small outputs, spread over the grid
     const uint32_t stride = gridDim.x * (uint32_t)kSupLanes;
     const uint32_t gid = blockIdx.x * (uint32_t)kSupLanes + tid;
@@ -293,7 +301,6 @@ inline uint32_t sup_groups(int32_t B, int32_t H, int32_t W)
 {
     return (uint32_t)(((uint64_t)B * H * W + kSupChunk - 1) / kSupChunk);
 }
-inline bool sup_aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
 
 }  // namespace gcfr
 
@@ -319,9 +326,8 @@ extern "C" int gcfr_supervised_losses_fwd(const float *depth, const float *gt_de
     hipStream_t st = (hipStream_t)stream;
     const uint32_t HW = (uint32_t)H * (uint32_t)W, N = (uint32_t)B * HW, groups = sup_groups(B, H, W);
     const uint32_t nl = logits ? (uint32_t)n_logits : 0u;
-    const int vec = HW % 4u == 0 && sup_aligned16(depth) && sup_aligned16(gt_depth) && sup_aligned16(mask) && sup_aligned16(albedo) &&
-                    sup_aligned16(gt_albedo) && sup_aligned16(mask_fill);
     double *partials = (double *)workspace;
+    const int vec = quad_vec_ok(HW, depth, gt_depth, mask, albedo, gt_albedo, mask_fill);
     hipLaunchKernelGGL(supervised_losses_fwd_kernel, dim3(groups), dim3(kSupLanes), 0, st, depth, gt_depth, mask, albedo, gt_albedo,
                        mask_fill, logits, nl, HW, N, vec, partials);
     hipLaunchKernelGGL(supervised_losses_finish_kernel, dim3(1), dim3(kSupLanes), 0, st, partials, groups, unit_light, ambient_values,
@@ -350,8 +356,7 @@ extern "C" int gcfr_supervised_losses_bwd(const float *depth, const float *gt_de
     a.grad_logits = grad_logits;
     a.n_logits = logits ? (uint32_t)n_logits : 0u;
     a.B = (uint32_t)B, a.HW = (uint32_t)H * (uint32_t)W, a.N = a.B * a.HW;
-    a.vec = a.HW % 4u == 0 && sup_aligned16(depth) && sup_aligned16(gt_depth) && sup_aligned16(mask) && sup_aligned16(albedo) &&
-            sup_aligned16(gt_albedo) && sup_aligned16(mask_fill) && sup_aligned16(grad_depth) && sup_aligned16(grad_albedo);
+    a.vec = quad_vec_ok(a.HW, depth, gt_depth, mask, albedo, gt_albedo, mask_fill, grad_depth, grad_albedo);
     hipLaunchKernelGGL(supervised_losses_bwd_kernel, dim3(sup_groups(B, H, W)), dim3(kSupLanes), 0, (hipStream_t)stream, a);
     return hipGetLastError() == hipSuccess ? GCFR_OK : GCFR_ERR_LAUNCH;
 }

@@ -29,18 +29,18 @@ def _launch_fwd(final, albedo, rgb, rendered, shading):
     dev = final.device
     with torch.cuda.device(dev):
         _lib.check(_lib.load().gcfr_light_rig_fwd(final.data_ptr(), albedo.data_ptr(), rgb.data_ptr(), rgb.shape[0], B, L, H, W,
-                                                  rendered.data_ptr(), shading.data_ptr(),
-                                                  torch.cuda.current_stream(dev).cuda_stream), "gcfr_light_rig_fwd")
+                                                  rendered.data_ptr(), shading.data_ptr(), _lib.stream_ptr(dev)),
+                   "gcfr_light_rig_fwd")
 
 
 def _launch_bwd(final, albedo, rgb, g_rendered, g_shading, g_final, g_albedo, g_rgb):
     B, L, H, W = final.shape
     dev = final.device
-    ptr = lambda t: None if t is None else t.data_ptr()
+    ptr = _lib.ptr
     with torch.cuda.device(dev):
         _lib.check(_lib.load().gcfr_light_rig_bwd(final.data_ptr(), albedo.data_ptr(), rgb.data_ptr(), rgb.shape[0], B, L, H, W,
                                                   ptr(g_rendered), ptr(g_shading), ptr(g_final), ptr(g_albedo), ptr(g_rgb),
-                                                  torch.cuda.current_stream(dev).cuda_stream), "gcfr_light_rig_bwd")
+                                                  _lib.stream_ptr(dev)), "gcfr_light_rig_bwd")
 
 
 class _CombineLightsFunction(torch.autograd.Function):
@@ -57,14 +57,13 @@ class _CombineLightsFunction(torch.autograd.Function):
         final, albedo, rgb = ctx.saved_tensors
         if g_rendered is None and g_shading is None:
             return None, None, None
-        f32c = lambda t: None if t is None else t.to(torch.float32).contiguous()
         want_final, want_albedo, want_rgb = ctx.needs_input_grad
         if not (want_final or want_albedo or want_rgb):
             return None, None, None
         g_final = torch.empty_like(final) if want_final else None
         g_albedo = torch.empty_like(albedo) if want_albedo else None
         g_rgb = torch.zeros(rgb.shape, dtype=torch.float64, device=rgb.device) if want_rgb else None      # accumulated in f64
-        _launch_bwd(final, albedo, rgb, f32c(g_rendered), f32c(g_shading), g_final, g_albedo, g_rgb)
+        _launch_bwd(final, albedo, rgb, _lib.f32c(g_rendered), _lib.f32c(g_shading), g_final, g_albedo, g_rgb)
         return g_final, g_albedo, (g_rgb.float() if want_rgb else None)
 
 
@@ -92,8 +91,7 @@ def _check_combine(final_shading, albedo, light_rgb):
     if light_rgb.dim() != 3 or tuple(light_rgb.shape[1:]) != (L, 3) or light_rgb.shape[0] not in (1, B):
         raise _lib.GcfrError("light_rgb must be (%d,%d,3) or (1,%d,3) for final_shading %s; got %s"
                              % (B, L, L, tuple(final_shading.shape), tuple(light_rgb.shape)))
-    if not final_shading.is_cuda:
-        raise _lib.GcfrError("geomconsistentfr_amd has no CPU path: tensors must be on a ROCm device")
+    _lib.require_device(final_shading)
 
 
 def combine_lights(final_shading: torch.Tensor, albedo: torch.Tensor, light_rgb: torch.Tensor):

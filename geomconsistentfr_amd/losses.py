@@ -52,10 +52,10 @@ class _ImageLossesFunction(torch.autograd.Function):
         ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=dev)
         win = _window()
         with torch.cuda.device(dev):
-            _lib.check(L_.gcfr_image_losses_fwd(rendered.data_ptr(), images.data_ptr(), mask.data_ptr() if mask is not None else None,
-                                                layout, B, H, W, ctypes.cast(win, ctypes.c_void_p), data_range, composite.data_ptr(),
-                                                ssim.data_ptr(), sums.data_ptr(), ws.data_ptr(), ws_bytes,
-                                                torch.cuda.current_stream(dev).cuda_stream), "gcfr_image_losses_fwd")
+            _lib.check(L_.gcfr_image_losses_fwd(rendered.data_ptr(), images.data_ptr(), _lib.ptr(mask), layout, B, H, W,
+                                                ctypes.cast(win, ctypes.c_void_p), data_range, composite.data_ptr(), ssim.data_ptr(),
+                                                sums.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev)),
+                       "gcfr_image_losses_fwd")
         recon_sq_sum, mask_sum = sums[0].float(), sums[1].float()
         ctx.save_for_backward(rendered, images, mask)
         ctx.layout, ctx.data_range = layout, data_range
@@ -69,16 +69,14 @@ class _ImageLossesFunction(torch.autograd.Function):
         L_ = _lib.load()
         B, _, H, W = rendered.shape
         dev = rendered.device
-        f32c = lambda t: None if t is None else t.to(torch.float32).contiguous()
-        g_composite, g_recon, g_ssim = f32c(g_composite), f32c(g_recon), f32c(g_ssim)
-        ptr = lambda t: t.data_ptr() if t is not None else None
+        ptr = _lib.ptr
+        g_composite, g_recon, g_ssim = _lib.f32c(g_composite), _lib.f32c(g_recon), _lib.f32c(g_ssim)
         grad = torch.empty_like(rendered)
         win = _window()
         with torch.cuda.device(dev):
             _lib.check(L_.gcfr_image_losses_bwd(rendered.data_ptr(), images.data_ptr(), ptr(mask), ctx.layout, B, H, W,
                                                 ctypes.cast(win, ctypes.c_void_p), ctx.data_range, ptr(g_composite), ptr(g_ssim),
-                                                ptr(g_recon), grad.data_ptr(), torch.cuda.current_stream(dev).cuda_stream),
-                       "gcfr_image_losses_bwd")
+                                                ptr(g_recon), grad.data_ptr(), _lib.stream_ptr(dev)), "gcfr_image_losses_bwd")
         return grad, None, None, None, None
 
 
@@ -92,8 +90,7 @@ def image_losses(rendered: torch.Tensor, images: torch.Tensor, masks_fill: torch
     if images_layout not in _LAYOUTS:
         raise ValueError("images_layout must be 'nhwc' or 'nchw', got %r" % (images_layout,))
     tensors = [t for t in (rendered, images, masks_fill) if t is not None]
-    if not all(t.is_cuda for t in tensors):
-        raise _lib.GcfrError("geomconsistentfr_amd has no CPU path: tensors must be on a ROCm device")
+    _lib.require_device(*tensors)
     if any(t.dtype != torch.float32 or t.device != rendered.device for t in tensors):
         raise _lib.GcfrError("image_losses: f32 tensors on one device")
     if images.requires_grad or (masks_fill is not None and masks_fill.requires_grad):
@@ -125,11 +122,10 @@ class _SupervisedLossesFunction(torch.autograd.Function):
         with torch.cuda.device(dev):
             _lib.check(L_.gcfr_supervised_losses_fwd(depth.data_ptr(), gt_depth.data_ptr(), mask.data_ptr(), albedo.data_ptr(),
                                                      gt_albedo.data_ptr(), mask_fill.data_ptr(), unit_light.data_ptr(),
-                                                     ambient_values.data_ptr(), lightings.data_ptr(),
-                                                     logits.data_ptr() if logits is not None else None,
+                                                     ambient_values.data_ptr(), lightings.data_ptr(), _lib.ptr(logits),
                                                      logits.numel() if logits is not None else 0, B, H, W, terms.data_ptr(),
-                                                     sums.data_ptr(), ws.data_ptr(), ws_bytes,
-                                                     torch.cuda.current_stream(dev).cuda_stream), "gcfr_supervised_losses_fwd")
+                                                     sums.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev)),
+                       "gcfr_supervised_losses_fwd")
         ctx.save_for_backward(depth, albedo, unit_light, ambient_values, logits, gt_depth, mask, gt_albedo, mask_fill, lightings, sums)
         return terms
 
@@ -147,12 +143,12 @@ class _SupervisedLossesFunction(torch.autograd.Function):
         with torch.cuda.device(dev):
             _lib.check(L_.gcfr_supervised_losses_bwd(depth.data_ptr(), gt_depth.data_ptr(), mask.data_ptr(), albedo.data_ptr(),
                                                      gt_albedo.data_ptr(), mask_fill.data_ptr(), ambient_values.data_ptr(),
-                                                     lightings.data_ptr(), logits.data_ptr() if logits is not None else None,
+                                                     lightings.data_ptr(), _lib.ptr(logits),
                                                      logits.numel() if logits is not None else 0, B, H, W, sums.data_ptr(),
                                                      gp[0], gp[1], gp[2], gp[3], gp[4] if logits is not None else None,
                                                      grad_depth.data_ptr(), grad_albedo.data_ptr(), grad_unit_light.data_ptr(),
-                                                     grad_ambient.data_ptr(), grad_logits.data_ptr() if logits is not None else None,
-                                                     torch.cuda.current_stream(dev).cuda_stream), "gcfr_supervised_losses_bwd")
+                                                     grad_ambient.data_ptr(), _lib.ptr(grad_logits), _lib.stream_ptr(dev)),
+                       "gcfr_supervised_losses_bwd")
         return grad_depth, grad_albedo, grad_unit_light, grad_ambient, grad_logits, None, None, None, None, None
 
 
@@ -169,8 +165,7 @@ def supervised_losses(depth: torch.Tensor, albedo: torch.Tensor, unit_light: tor
     require grad."""
     gts = [batch[k] for k in _SUPERVISED_BATCH_KEYS] + [batch["lightings"]]
     tensors = [depth, albedo, unit_light, ambient_values] + gts + ([logits_fake] if logits_fake is not None else [])
-    if not all(t.is_cuda for t in tensors):
-        raise _lib.GcfrError("geomconsistentfr_amd has no CPU path: tensors must be on a ROCm device")
+    _lib.require_device(*tensors)
     if any(t.dtype != torch.float32 or t.device != depth.device for t in tensors):
         raise _lib.GcfrError("supervised_losses: f32 tensors on one device")
     if any(t.requires_grad for t in gts):

@@ -15,13 +15,10 @@ Every array that enters or leaves an arithmetic operation is asserted to be floa
 compute in f64 without noticing."""
 import numpy as np
 
-F32 = np.float32
+import f32_bits
+from f32_bits import F32, _f, bit_equal_any_nan as bit_equal  # noqa: F401  (bit_equal: for the tests; the kernel's NaN is not numpy's)
+
 WIN, WIN_R = 11, 5
-
-
-def _f(a):
-    assert isinstance(a, (np.ndarray, np.generic)) and a.dtype == np.float32, getattr(a, "dtype", type(a))
-    return a
 
 
 def gauss_window():
@@ -152,17 +149,6 @@ def backward_selections(rendered, images_nchw, mask, window, data_range, g_compo
 
 
 def ulps(a, b):
-    """distance in f32 units in the last place between two finite f32 arrays (0 for +0 / -0)"""
-    a, b = _f(np.asarray(a, F32)), _f(np.asarray(b, F32))
+    """`f32_bits.ulps` between two FINITE f32 arrays"""
     assert np.isfinite(a).all() and np.isfinite(b).all()
-    key = lambda v: np.where(v.view(np.int32) < 0, np.int64(-2 ** 31) - v.view(np.int32).astype(np.int64), v.view(np.int32).astype(np.int64))
-    return np.abs(key(a) - key(b))
-
-
-def bit_equal(a, b):
-    """the same f32 bits (the sign of a zero included); a NaN equals a NaN of any payload"""
-    a, b = _f(np.ascontiguousarray(a)), _f(np.ascontiguousarray(b))
-    if a.shape != b.shape:
-        return False
-    nan = np.isnan(a)
-    return bool(np.array_equal(nan, np.isnan(b)) and np.array_equal(a.view(np.int32)[~nan], b.view(np.int32)[~nan]))
+    return f32_bits.ulps(a, b)

@@ -8,12 +8,7 @@ Arrays are float32 in the C ABI's layouts: final (B,L,H,W), albedo (B,3,H,W), rg
 g_rendered / g_shading (B,3,H,W) or None each."""
 import numpy as np
 
-F32 = np.float32
-
-
-def _f(a):
-    assert isinstance(a, (np.ndarray, np.generic)) and a.dtype == np.float32, getattr(a, "dtype", type(a))
-    return a
+from f32_bits import F32, _f, bit_equal  # noqa: F401  (bit_equal: for the tests)
 
 
 def _shapes(final, albedo, rgb):
@@ -77,8 +72,3 @@ def backward(final, albedo, rgb, g_rendered, g_shading):
         if rgb.shape[0] == 1:
             s, a = s.sum(axis=0, keepdims=True), a.sum(axis=0, keepdims=True)
     return {"g_final": g_final, "g_albedo": g_albedo, "g_rgb": s.astype(F32), "g_rgb_f64": s, "g_rgb_bound": a * 2.0 ** -23}
-
-
-def bit_equal(a, b):
-    a, b = np.ascontiguousarray(_f(a)), np.ascontiguousarray(_f(b))
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))

@@ -8,14 +8,10 @@ Arrays are float32 in the C ABI's layouts: depth, gt_depth, mask, gt_albedo, mas
 ambient (B,); lightings (B,4); logits any shape or None."""
 import numpy as np
 
-F32 = np.float32
+from f32_bits import F32, _f, bit_equal, ulps  # noqa: F401  (bit_equal, ulps: for the tests)
+
 THIRD = F32(1.0) / F32(3.0)
 TERMS = ("depth", "ambient", "lighting", "albedo", "generator")
-
-
-def _f(a):
-    assert isinstance(a, (np.ndarray, np.generic)) and a.dtype == np.float32, getattr(a, "dtype", type(a))
-    return a
 
 
 def sgn(d):
@@ -106,14 +102,3 @@ def backward(depth, gt_depth, mask, albedo, gt_albedo, mask_fill, ambient, light
                 s = (g_g * F32(0.01)) / F32(x.size)
                 out["logits"] = _f(s * -(F32(1.0) / _f(F32(1.0) + exp_plain(x))))
     return {k: _f(np.ascontiguousarray(v)) for k, v in out.items()}
-
-
-def ulps(a, b):
-    """distance of two float32 values in units in the last place (sign-magnitude order; +0 and -0 are 0 apart)"""
-    key = lambda v: (lambda i: np.where(i < 0, np.int64(-(2 ** 31)) - i, i))(np.asarray(v, F32).view(np.int32).astype(np.int64))
-    return np.abs(key(a) - key(b))
-
-
-def bit_equal(a, b):
-    a, b = np.ascontiguousarray(_f(a)), np.ascontiguousarray(_f(b))
-    return a.shape == b.shape and np.array_equal(a.view(np.uint32), b.view(np.uint32))
