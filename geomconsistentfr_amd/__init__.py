@@ -7,5 +7,7 @@ the reference's only callable boundary, RelightNet.forward.
 """
 from .block import RenderParams, render, shadow_min_distance, light_prep  # noqa: F401
 from .lighting import area_light, combine_lights, render_rig_from_depth  # noqa: F401
+from .lighting import (environment_lights, environment_tables, render_environment_from_depth,  # noqa: F401
+                       sphere_directions)
 
 __version__ = "0.5.0"   # = the library's (gcfr_version(): "gcfr-hip 0.5.0 gfx950")

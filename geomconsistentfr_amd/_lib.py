@@ -111,6 +111,9 @@ _SIGNATURES = {
                                         _p, _p, _p, _p]),
     "gcfr_light_rig_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p]),
     "gcfr_light_rig_bwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "gcfr_environment_cells": (_i, [_p, _p, _p, _i, _i, _i, _f, _p, _p]),
+    "gcfr_environment_fwd": (_i, [_p, _i, _i, _i, _p, _p, _i, _p, _p]),
+    "gcfr_environment_bwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _p]),
     "gcfr_copy_probe": (_i, [_p, _p, ctypes.c_size_t, _p]),
 }
 

@@ -184,6 +184,92 @@ def relight_rig(model, images, mask_u8, lights, light_rgb, ambient: float = 0.5,
                               epoch).cpu().numpy()
 
 
+def _as_environment(env, device) -> torch.Tensor:
+    """a lat-long radiance map as a contiguous f32 device tensor (1|B,He,We,3); (He,We,3) is one map shared by all faces"""
+    t = (env if torch.is_tensor(env) else torch.as_tensor(np.asarray(env, np.float32))).to(device=device, dtype=torch.float32)
+    return (t[None] if t.dim() == 3 else t).contiguous()
+
+
+def _environment_directions(n_lights, min_z, device) -> torch.Tensor:
+    from .lighting import sphere_directions
+    return torch.from_numpy(sphere_directions(n_lights, min_z)).to(device)
+
+
+def _lights_pass(model, x, mask_u8, lights, ambient, focal, device, composite_mask_u8, epoch):
+    """ONE `forward_lights` pass of `x` (B,H,W,3, on the device) under `lights` (L,3) | (B,L,3), exactly as `relight_rig_device`
+    runs it (keep the two in step: the environment entries are held byte for byte to `relight_rig_device`).  Returns three values:
+    `out`, the tuple `model.forward_lights` returned; `cm`, the compositing mask as a uint8 device tensor (`composite_mask_u8`, or
+    `mask_u8` where that is None); `transfer`, True if `model` is a RelightNetLightingTransfer."""
+    B, H, W, _ = x.shape
+    transfer = _is_transfer(model)
+    K = camera_matrix((700.0 if transfer else 1570.0) if focal is None else focal, H, W)          # host: read without a sync
+    as_u8 = lambda m: (m if torch.is_tensor(m) else torch.as_tensor(np.asarray(m))).to(device=device, dtype=torch.uint8)
+    m_u8 = as_u8(mask_u8)
+    mask = (m_u8.to(torch.float64).reshape(H, W, 1) / 255.0)                                                     # S1:580 / SLT:540
+    lights = (lights if torch.is_tensor(lights) else torch.as_tensor(np.asarray(lights, np.float32))).to(device=device, dtype=torch.float32)
+    lights = lights.reshape(-1, 3) if lights.dim() <= 2 else lights
+    out = model.forward_lights(x, epoch, K, mask, lights, float(ambient)) if transfer else model.forward_lights(x, epoch, K, mask, lights)
+    return out, (m_u8 if composite_mask_u8 is None else as_u8(composite_mask_u8)), transfer
+
+
+@torch.no_grad()
+def relight_environment_device(model, images, mask_u8, env, n_lights: int = 64, rotation=None, min_cos: float = -2.0,
+                               min_z: float = 0.2, ambient: float = 0.5, focal: float = None, device="cuda",
+                               fix_border: bool = False, composite_mask_u8=None, epoch: int = 200) -> torch.Tensor:
+    """`relight_environment` up to the bytes ON THE DEVICE: (B,H,W,3) uint8 tensor, nothing copied back.  `images` / `mask_u8` /
+    `env` / `rotation` may already be device tensors."""
+    from .lighting import _check_environment, environment_lights
+    x = _as_batch(images).to(device)
+    directions = _environment_directions(n_lights, min_z, x.device)
+    env_d = _as_environment(env, x.device)
+    rot = None if rotation is None else torch.as_tensor(rotation, dtype=torch.float32)
+    _check_environment(env_d, directions, rot, None, faces=x.shape[0])                # a malformed map fails before the network pass
+    out, cm, transfer = _lights_pass(model, x, mask_u8, directions, ambient, focal, device, composite_mask_u8, epoch)
+    return _rig_composites(x, out, cm, environment_lights(env_d, directions, rot, min_cos), transfer, fix_border)
+
+
+@torch.no_grad()
+def relight_environment(model, images, mask_u8, env, n_lights: int = 64, rotation=None, min_cos: float = -2.0,
+                        min_z: float = 0.2, ambient: float = 0.5, focal: float = None, device="cuda", fix_border: bool = False,
+                        composite_mask_u8=None, epoch: int = 200) -> np.ndarray:
+    """Every face of `images` (B,H,W,3) under the lat-long radiance map `env` (He,We,3) | (1,He,We,3) | (B,He,We,3) as ONE
+    (B,H,W,3) uint8 RGB composite per face.  The map is integrated into a rig of `n_lights` fixed directions
+    (`lighting.sphere_directions(n_lights, min_z)`, the part of the sphere in front of the face) by `lighting.environment_lights`:
+    one network pass (`forward_lights`) over those directions, the stage, then `relight_rig`'s combine, image kernel and optional
+    border fix.  `rotation` (3,3) turns the environment around the face (`environment_lights` states its sense), `min_cos` as
+    there.  The map's frame and layout: `lighting.environment_tables`.  The weights of the whole sphere sum to 1, so a constant
+    map of radiance 1 counts the ambient term once.  `model` / `ambient` / `focal` as in `relight_lights`.  One device-to-host
+    copy of B*H*W*3 bytes at the end."""
+    return relight_environment_device(model, images, mask_u8, env, n_lights, rotation, min_cos, min_z, ambient, focal, device,
+                                      fix_border, composite_mask_u8, epoch).cpu().numpy()
+
+
+@torch.no_grad()
+def relight_environment_frames(model, images, mask_u8, env, rotations, n_lights: int = 64, min_cos: float = -2.0,
+                               min_z: float = 0.2, ambient: float = 0.5, focal: float = None, device="cuda",
+                               fix_border: bool = False, composite_mask_u8=None, epoch: int = 200) -> torch.Tensor:
+    """A turntable: every face of `images` under `env` rotated by each of `rotations` (F,3,3), as a (B,F,H,W,3) uint8 DEVICE
+    tensor; frame f equals `relight_environment_device(..., rotation=rotations[f])` byte for byte, given the same network outputs.
+    The rig's directions are fixed in the face's frame and a rotation changes `light_rgb` only, so the whole turntable is ONE
+    network pass and L marches.  The F rotated direction sets are F small matmuls issued before the frames (the single call's own
+    `directions @ rotation`, so that the cell maps cannot differ from its in a last bit).  Per frame four launches -- the cell
+    map, the integration, the rig combine, the image kernel -- and a fifth with `fix_border`; one more in total stacks the
+    frames."""
+    from ._lib import GcfrError
+    from .lighting import _check_environment, _environment_lights
+    x = _as_batch(images).to(device)
+    directions = _environment_directions(n_lights, min_z, x.device)
+    rots = torch.as_tensor(rotations, dtype=torch.float32).to(x.device)
+    if rots.dim() != 3 or tuple(rots.shape[1:]) != (3, 3) or rots.shape[0] < 1:
+        raise GcfrError("rotations must be (F,3,3) with F >= 1; got %s" % (tuple(rots.shape),))
+    env_d = _as_environment(env, x.device)
+    _check_environment(env_d, directions, None, None, faces=x.shape[0])               # a malformed map fails before the network pass
+    out, cm, transfer = _lights_pass(model, x, mask_u8, directions, ambient, focal, device, composite_mask_u8, epoch)
+    dirs_map = [directions @ rots[f] for f in range(rots.shape[0])]
+    frames = [_rig_composites(x, out, cm, _environment_lights(env_d, d, min_cos, None), transfer, fix_border) for d in dirs_map]
+    return torch.stack(frames, dim=1)
+
+
 def fold_batchnorm(model):
     """An EVAL-mode copy of a RelightNet* model with every BatchNorm folded into the convolution in front of it.
 

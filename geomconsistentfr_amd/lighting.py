@@ -12,6 +12,15 @@ to 1 count the ambient once.  One fused HIP launch forward and one backward; the
     combine_lights          the operation, differentiable with respect to final_shading, albedo and light_rgb
     render_rig_from_depth   block.render_from_depth in its many-lights form + combine_lights on its final_shading
     area_light              n directions on a spherical cap (a deterministic Fibonacci spiral) and their weights, on the host
+
+Environment maps (csrc/gcfr_environment.hip): a lat-long radiance map becomes the `light_rgb` of a rig of L fixed directions -- every
+texel belongs to the direction nearest to it, a light's rgb is the solid-angle-weighted sum of its texels.  Rotating the map changes
+`light_rgb` only, so a turntable needs one network pass and L marches in total.
+
+    environment_tables             the map's trigonometry and solid-angle weights, on the host (no kernel evaluates a sine)
+    sphere_directions              n directions on the part of the sphere the block can light from (a deterministic Fibonacci spiral)
+    environment_lights             the stage: map + directions (+ rotation) -> light_rgb, differentiable with respect to the map
+    render_environment_from_depth  render_rig_from_depth with light_rgb taken from the stage
 """
 import math
 
@@ -179,3 +188,191 @@ def area_light(direction, angular_radius_deg: float, n: int, colour=(1.0, 1.0, 1
     else:
         raise ValueError("area_light: no spiral of %d points fits the cap of %r degrees" % (n, angular_radius_deg))
     return pts.astype(np.float32), rgb
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# environment maps
+# ------------------------------------------------------------------------------------------------------------------------------
+MAX_TEXELS = 1 << 24   # include/gcfr.h: He We <= 2^24
+
+
+def environment_tables(He: int, We: int):
+    """The tables the environment kernels read instead of evaluating trigonometry, for a lat-long map of He rows and We columns:
+    (rows (He,2) f32 = sin, cos theta_r; row_w (He,) f64; cols (We,2) f32 = sin, cos phi_c), computed on the host in f64 and
+    rounded once.  Texel (r, c) looks along omega = (sin theta sin phi, cos theta, sin theta cos phi) in the block's frame, the
+    one light directions are given in: +x towards the image's right (increasing column), +y UP in the image (towards row 0 of the
+    photograph: `LIGHT_DIRECTIONS["top_A00E45"]` has y > 0), +z from the face towards the camera.
+    theta_r = pi (r + 1/2) / He is measured from +y: row 0 of the map is the sky above the head, the last row the ground.
+    phi_c = 2 pi (c + 1/2) / We - pi: the map's centre column faces +z, the side the camera and the front lights are on; columns
+    right of the centre have omega_x > 0, and the two outer columns meet behind the head.
+    row_w[r] = (cos theta_top - cos theta_bottom) / (2 We) with theta_top = pi r / He, theta_bottom = pi (r + 1) / He: the band's
+    exact solid angle per texel over 4 pi, so the weights of all He We texels sum to 1 and a constant map of radiance 1 gives
+    weights that count the rig stage's ambient term once."""
+    He, We = int(He), int(We)
+    if He < 1 or We < 1 or He * We > MAX_TEXELS:
+        raise ValueError("environment_tables: He, We >= 1 and He We <= 2^24; got %d x %d" % (He, We))
+    theta = math.pi * (np.arange(He, dtype=np.float64) + 0.5) / He
+    edge = np.cos(math.pi * np.arange(He + 1, dtype=np.float64) / He)
+    edge[0], edge[-1] = 1.0, -1.0
+    phi = 2.0 * math.pi * (np.arange(We, dtype=np.float64) + 0.5) / We - math.pi
+    rows = np.stack([np.sin(theta), np.cos(theta)], axis=1).astype(np.float32)
+    cols = np.stack([np.sin(phi), np.cos(phi)], axis=1).astype(np.float32)
+    return rows, (edge[:-1] - edge[1:]) / (2.0 * We), cols
+
+
+def sphere_directions(n: int, min_z: float = 0.2) -> np.ndarray:
+    """n unit directions (n,3) f32 on the part z >= min_z of the sphere, an equal-area Fibonacci spiral: point i at
+    z_i = 1 - (1 - min_z)(i + 1/2) / n (every point strictly inside the cap) and at azimuth i times the golden angle.
+    Deterministic, computed on the host in f64 and rounded once.  The default keeps clear of the lighting-transfer model's clamp
+    of a light's z (`clamp_min` 0.16), so that the block lights the face from where the map's cell is; min_z = -1 gives the whole
+    sphere (lights behind the face shade nothing but still take their share of the map)."""
+    n, min_z = int(n), float(min_z)
+    if not 1 <= n <= MAX_LIGHTS:
+        raise ValueError("sphere_directions: 1 <= n <= %d; got %d" % (MAX_LIGHTS, n))
+    if not -1.0 <= min_z < 1.0:
+        raise ValueError("sphere_directions: min_z in [-1, 1); got %r" % (min_z,))
+    i = np.arange(n, dtype=np.float64)
+    z = 1.0 - (1.0 - min_z) * (i + 0.5) / n
+    s = np.sqrt(np.maximum(0.0, 1.0 - z * z))
+    phi = i * (math.pi * (3.0 - math.sqrt(5.0)))
+    return np.stack([s * np.cos(phi), s * np.sin(phi), z], axis=1).astype(np.float32)
+
+
+_ENV_TABLES = {}       # (He, We, device) -> (rows, row_w, cols) on the device: uploaded once, never written, never evicted
+
+
+def _device_tables(He, We, device):
+    """the tables of a (He, We) map on `device`.  The FIRST call per (He, We, device) builds them on the host and uploads them (a
+    pageable host-to-device copy: not for a stream that is being captured); every later call only looks them up"""
+    key = (He, We, str(device))
+    if key not in _ENV_TABLES:
+        _ENV_TABLES[key] = tuple(torch.from_numpy(a).to(device) for a in environment_tables(He, We))
+    return _ENV_TABLES[key]
+
+
+def _launch_env_cells(rows, cols, dirs_map, He, We, min_cos, cell):
+    dev = dirs_map.device
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().gcfr_environment_cells(rows.data_ptr(), cols.data_ptr(), dirs_map.data_ptr(), He, We, dirs_map.shape[0],
+                                                      float(min_cos), cell.data_ptr(), _lib.stream_ptr(dev)), "gcfr_environment_cells")
+
+
+def _launch_env_fwd(env, row_w, cell, L, rgb):
+    E, He, We, _ = env.shape
+    dev = env.device
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().gcfr_environment_fwd(env.data_ptr(), E, He, We, row_w.data_ptr(), cell.data_ptr(), L, rgb.data_ptr(),
+                                                    _lib.stream_ptr(dev)), "gcfr_environment_fwd")
+
+
+def _launch_env_bwd(g_rgb, row_w, cell, g_env):
+    E, He, We, _ = g_env.shape
+    dev = g_env.device
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().gcfr_environment_bwd(g_rgb.data_ptr(), row_w.data_ptr(), cell.data_ptr(), E, He, We, g_rgb.shape[1],
+                                                    g_env.data_ptr(), _lib.stream_ptr(dev)), "gcfr_environment_bwd")
+
+
+class _EnvironmentLightsFunction(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, env, dirs_map, min_cos, out):
+        E, He, We, _ = env.shape
+        L = dirs_map.shape[0]
+        rows, row_w, cols = _device_tables(He, We, env.device)
+        cell = torch.empty((He, We), dtype=torch.int32, device=env.device)
+        rgb = torch.empty((E, L, 3), dtype=torch.float32, device=env.device) if out is None else out
+        _launch_env_cells(rows, cols, dirs_map, He, We, min_cos, cell)
+        _launch_env_fwd(env, row_w, cell, L, rgb)
+        ctx.save_for_backward(row_w, cell)
+        ctx.env_shape = tuple(env.shape)
+        if out is not None:
+            ctx.mark_dirty(out)
+        return rgb
+
+    @staticmethod
+    def backward(ctx, g_rgb):
+        row_w, cell = ctx.saved_tensors
+        if g_rgb is None or not ctx.needs_input_grad[0]:
+            return None, None, None, None
+        g_env = torch.empty(ctx.env_shape, dtype=torch.float32, device=cell.device)
+        _launch_env_bwd(_lib.f32c(g_rgb), row_w, cell, g_env)
+        return g_env, None, None, None          # (no gradient to the directions: the cell map is piecewise constant in them)
+
+
+def _check_environment(env, directions, rotation, out, faces=None):
+    """Every shape, dtype and device BEFORE anything is launched or loaded: a mismatch never reaches the kernels.  `faces`: the
+    batch the maps are for (E must be 1 or that)."""
+    named = [("env", env), ("directions", directions)] + ([("rotation", rotation)] if rotation is not None else []) \
+        + ([("out", out)] if out is not None else [])
+    for n, t in named:
+        if not torch.is_tensor(t):
+            raise _lib.GcfrError("environment_lights: %s must be a tensor, got %s" % (n, type(t).__name__))
+        if t.dtype != torch.float32:
+            raise _lib.GcfrError("environment_lights: %s must be float32, got %s" % (n, t.dtype))
+    if env.dim() != 4 or env.shape[3] != 3:
+        raise _lib.GcfrError("env must be (E,He,We,3) -- a lat-long map per face, or E = 1 for one map; got %s" % (tuple(env.shape),))
+    E, He, We, _ = env.shape
+    if E < 1 or He < 1 or We < 1 or He * We > MAX_TEXELS:
+        raise _lib.GcfrError("env (E,He,We,3) = %s: E, He, We >= 1 and He We <= 2^24" % (tuple(env.shape),))
+    if faces is not None and E not in (1, faces):
+        raise _lib.GcfrError("env must be (1,He,We,3) or (%d,He,We,3) for %d faces; got %s" % (faces, faces, tuple(env.shape)))
+    if directions.dim() != 2 or directions.shape[1] != 3 or not 1 <= directions.shape[0] <= MAX_LIGHTS:
+        raise _lib.GcfrError("directions must be (L,3) with 1 <= L <= %d; got %s" % (MAX_LIGHTS, tuple(directions.shape)))
+    if rotation is not None and tuple(rotation.shape) != (3, 3):
+        raise _lib.GcfrError("rotation must be (3,3); got %s" % (tuple(rotation.shape),))
+    if directions.device != env.device:
+        raise _lib.GcfrError("environment_lights: env and directions on one device; got %s, %s" % (env.device, directions.device))
+    if out is not None:
+        if tuple(out.shape) != (E, directions.shape[0], 3) or out.device != env.device or not out.is_contiguous():
+            raise _lib.GcfrError("out must be a contiguous (%d,%d,3) tensor on %s; got %s on %s"
+                                 % (E, directions.shape[0], env.device, tuple(out.shape), out.device))
+        if out.requires_grad:
+            raise _lib.GcfrError("out must not require a gradient: it is a buffer the result is written into")
+    _lib.require_device(env, directions, out)
+
+
+def environment_lights(env: torch.Tensor, directions: torch.Tensor, rotation=None, min_cos: float = -2.0, out=None):
+    """`light_rgb` (E,L,3) of the lat-long radiance map(s) `env` (E,He,We,3) for the rig of `directions` (L,3): every texel
+    belongs to the direction nearest to it (largest dot product; a tie goes to the lowest index) and a light's rgb is the sum of
+    its texels' radiance times their solid angle over 4 pi (`environment_tables`).  E = 1 is one map for all faces, E = B one per
+    face -- what `combine_lights` takes.  All f32 tensors on one ROCm device.  Nothing is clamped: negative radiance is legal, a
+    non-finite texel reaches its own light's entry only.
+    `rotation` (3,3), a device or host tensor: the rig is looked up in the map at `directions @ rotation`.  With R = rotation
+    as a matrix acting on column vectors, what the map shows in direction m lights the face from R m: R = I leaves the map's
+    centre column in front of the face, a rotation about +y by an angle a turns the environment around the head by a.  The
+    product is torch's, on the device; a host `rotation` is uploaded first (pass a device tensor to keep the call asynchronous).
+    `min_cos`: a texel whose best dot product is below it belongs to no light (the default drops nothing); its radiance is
+    then not counted, so the weights no longer sum to 1.
+    `out`: a contiguous (E,L,3) f32 buffer the result is written into and which is returned -- `RelightSession.light_rgb`
+    between two replays, for example: no output is allocated and the host never waits.
+    The tables of a map size are uploaded by the first call for that (He, We, device) and kept for the life of the process
+    (three small tensors per size).  Make that first call OUTSIDE a stream capture -- a warm-up call on the same map size does
+    it -- since the upload is a pageable host-to-device copy; every later call launches the two kernels and nothing else.
+    Differentiable with respect to `env` (a gather of the upstream gradient); the directions and the rotation receive no
+    gradient, the cell assignment being piecewise constant in them.  Two launches forward, one backward; the order of the
+    f64 sum is fixed (include/gcfr.h), so equal inputs give equal bits.  A malformed input raises GcfrError before any launch."""
+    _check_environment(env, directions, rotation, out)
+    dirs_map = directions.detach()
+    if rotation is not None:
+        dirs_map = dirs_map @ rotation.detach().to(env.device)
+    return _environment_lights(env, dirs_map, min_cos, out)
+
+
+def _environment_lights(env, dirs_map, min_cos, out):
+    """environment_lights behind its checks, on directions already in the map's frame"""
+    return _EnvironmentLightsFunction.apply(env.contiguous(), dirs_map.contiguous(), float(min_cos), out)
+
+
+def render_environment_from_depth(depth, albedo, directions, ambient, env, camera_matrix, z_offset, mask,
+                                  params: RenderParams = RenderParams(), prepared=None, rotation=None, min_cos: float = -2.0):
+    """`render_rig_from_depth` with the rig's `light_rgb` taken from `environment_lights(env, directions, rotation, min_cos)`:
+    every face is lit from the L `directions` (L,3) (ambient (B,L), the many-lights form) and the per-light shadings are combined
+    with the map's colour x weight per light.  `env` (1,He,We,3) is one map for all faces, (B,He,We,3) one per face.  Returns
+    that call's dict plus `light_rgb` (E,L,3).  Gradients reach depth, albedo, ambient and `env`."""
+    B = depth.shape[0]
+    _check_environment(env, directions, rotation, None, faces=B)
+    light_rgb = environment_lights(env, directions, rotation, min_cos)
+    light = directions.detach()[None].expand(B, -1, -1).contiguous()
+    r = render_rig_from_depth(depth, albedo, light, ambient, light_rgb, camera_matrix, z_offset, mask, params, prepared=prepared)
+    r["light_rgb"] = light_rgb
+    return r

@@ -582,6 +582,55 @@ int gcfr_light_rig_bwd(const float *final_shading, const float *albedo, const fl
                        double *g_rgb, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Environment-map lighting: a lat-long radiance map integrated into the `rgb` (colour x weight per light) of the light-rig stage
+ * above (csrc/gcfr_environment.hip).  Every texel belongs to the light direction nearest to it; a light's rgb is the
+ * solid-angle-weighted sum of its texels.  No kernel evaluates a transcendental function: the trigonometry arrives in host-built
+ * tables (lighting.environment_tables), all contiguous:
+ *   rows     (He,2) f32   sin, cos of row r's polar angle theta_r = pi (r + 1/2) / He, measured from +y
+ *   cols     (We,2) f32   sin, cos of column c's azimuth phi_c = 2 pi (c + 1/2) / We - pi (the centre column faces +z)
+ *   row_w    (He,)  F64   the row's solid angle per texel over 4 pi: (cos theta_top - cos theta_bottom) / (2 We); 8-byte aligned
+ *   dirs_map (L,3)  f32   the light directions IN THE MAP'S FRAME (a rotation is the caller's matmul; nothing is rotated here)
+ *   cell     (He,We) i32  the index of the texel's light, or -1
+ * 1 <= L <= 4096, He, We >= 1 with He We <= 2^24, 1 <= E <= 65535; anything else, a NULL pointer or a misaligned row_w is
+ * GCFR_ERR_INVALID_ARGUMENT before a launch.  The entries allocate nothing and never synchronise.
+ * ------------------------------------------------------------------------------------------- */
+
+/*
+ * The cell map, one launch.  Per texel (row r, column c): omega = (sin_t sin_p, cos_t, sin_t cos_p), each product one f32 operation;
+ * best = -inf, cell = -1; for l = 0 .. L-1 ascending: s = (omega_x d_x + omega_y d_y) + omega_z d_z, every product and sum one
+ * IEEE f32 operation (no contraction); if (s > best) { best = s; cell = l; } -- a tie keeps the lowest index, a NaN score never
+ * wins (nor does -inf); afterwards if (!(best >= min_cos)) cell = -1.  min_cos <= -1 drops nothing but texels without any finite
+ * score; min_cos > 1 drops every texel.  Bit-equal to the numpy restatement (tests/environment_emulation.py).
+ */
+int gcfr_environment_cells(const float *rows, const float *cols, const float *dirs_map, int32_t He, int32_t We, int32_t L,
+                           float min_cos, int32_t *cell_out, void *stream);
+
+/*
+ * The integration, one launch:   env (E,He,We,3) f32 radiance   ->   rgb_out (E,L,3) f32,
+ *   rgb_out[e,l,c] = (float) sum_{t : cell[t] == l} (double)env[e,t,c] * row_w[row(t)]          t = r We + c, row(t) = t / We
+ * The products and the sum are f64 operations (unfused), in a FIXED order: one workgroup of 256 lanes per (e, l); lane i adds the
+ * texels i, i + 256, i + 512, ... of the cell in ascending order to a sum that starts at +0; the 256 sums are added as each
+ * wave's xor-shuffle tree (offsets 32, 16, ..., 1), then the four waves as (w0 + w1) + (w2 + w3); one rounding to f32.  No
+ * floating-point atomic: every element of rgb_out is written exactly once, an empty cell gives +0, two calls on the same inputs
+ * return the same bits, and the result equals the restatement of this order bit for bit.  Nothing is clamped (negative radiance
+ * is legal); a non-finite texel propagates into its own cell's entry of that channel and map, and nowhere else.  The weights of
+ * all texels sum to 1: a constant map of radiance 1 whose every texel has a cell gives sum_l rgb = 1.  cell values outside
+ * [0, L) belong to no light.
+ */
+int gcfr_environment_fwd(const float *env, int32_t E, int32_t He, int32_t We, const double *row_w, const int32_t *cell, int32_t L,
+                         float *rgb_out, void *stream);
+
+/*
+ * Backward of the integration with respect to the radiance, one launch, a gather:   g_rgb (E,L,3) f32   ->   g_env (E,He,We,3) f32,
+ *   g_env[e,t,c] = (float)row_w[row(t)] * g_rgb[e,cell[t],c]      one f32 product;   +0 where cell[t] is -1 (or outside [0, L))
+ * Every element is written once (no accumulation: the caller clears nothing).  There is NO gradient with respect to the
+ * directions: the cell assignment is piecewise constant in them (its derivative is zero almost everywhere and undefined on the
+ * cell borders), so gcfr_environment_cells has no backward.
+ */
+int gcfr_environment_bwd(const float *g_rgb, const double *row_w, const int32_t *cell, int32_t E, int32_t He, int32_t We, int32_t L,
+                         float *g_env, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Measurement aid (bench.py `roofline.hbm_measured_copy_GBs`): a float4 grid-stride device-to-device copy of `bytes` bytes
  * (multiple of 16, both pointers 16-byte aligned), one workgroup of 256 lanes per CU, four loads in flight per lane, non-temporal --
  * the achievable-HBM probe (6.3 TB/s, read + write) the roofline's 8 TB/s spec peak is reported beside.  Not part of the render path.
