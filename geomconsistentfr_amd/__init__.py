@@ -9,5 +9,6 @@ from .block import RenderParams, render, shadow_min_distance, light_prep  # noqa
 from .lighting import area_light, combine_lights, render_rig_from_depth  # noqa: F401
 from .lighting import (environment_lights, environment_tables, render_environment_from_depth,  # noqa: F401
                        sphere_directions)
+from .lighting import fit_light_rgb, light_normal_equations  # noqa: F401
 
 __version__ = "0.5.0"   # = the library's (gcfr_version(): "gcfr-hip 0.5.0 gfx950")

@@ -114,6 +114,9 @@ _SIGNATURES = {
     "gcfr_environment_cells": (_i, [_p, _p, _p, _i, _i, _i, _f, _p, _p]),
     "gcfr_environment_fwd": (_i, [_p, _i, _i, _i, _p, _p, _i, _p, _p]),
     "gcfr_environment_bwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _p]),
+    "gcfr_light_fit_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i, _i]),
+    "gcfr_light_fit_normal": (_i, [_p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
+    "gcfr_light_fit_solve": (_i, [_p, _p, _i, _i, _d, _i, _p, _p, _p]),
     "gcfr_copy_probe": (_i, [_p, _p, ctypes.c_size_t, _p]),
 }
 

@@ -21,6 +21,12 @@ texel belongs to the direction nearest to it, a light's rgb is the solid-angle-w
     sphere_directions              n directions on the part of the sphere the block can light from (a deterministic Fibonacci spiral)
     environment_lights             the stage: map + directions (+ rotation) -> light_rgb, differentiable with respect to the map
     render_environment_from_depth  render_rig_from_depth with light_rgb taken from the stage
+
+Rig capture (csrc/gcfr_light_fit.hip), the inverse of the rig stage: the `light_rgb` under which the per-light shadings come closest
+to a photograph, a weighted least-squares problem per face and channel -- "light this face like that photograph".
+
+    light_normal_equations         the weighted Gram matrix and right-hand side over all pixels, f64 in a fixed order
+    fit_light_rgb                  the normal equations + a Cholesky solve with a relative ridge -> light_rgb (not differentiable)
 """
 import math
 
@@ -376,3 +382,141 @@ def render_environment_from_depth(depth, albedo, directions, ambient, env, camer
     r = render_rig_from_depth(depth, albedo, light, ambient, light_rgb, camera_matrix, z_offset, mask, params, prepared=prepared)
     r["light_rgb"] = light_rgb
     return r
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# rig capture: light_rgb fitted to a photograph
+# ------------------------------------------------------------------------------------------------------------------------------
+MAX_FIT_LIGHTS = 64            # include/gcfr.h: 1 <= L <= 64 for the fit
+LIGHT_FIT_CHUNK = 64           # csrc/gcfr_light_fit.hip kFitChunk: pixels per chunk
+LIGHT_FIT_MAX_GROUPS = 512     # ... kFitMaxGroups: workgroups per launch at the most
+
+
+def light_fit_geometry(B: int, H: int, W: int):
+    """(chunk, groups) of gcfr_light_fit_normal for B faces of H x W: the face's pixels are cut into chunks of `chunk` consecutive
+    pixels and workgroup g of the face's `groups` sums the chunks g, g + groups, ... (include/gcfr.h).  The restatement
+    (tests/light_fit_emulation.py) takes the two as parameters; the host test holds them to gcfr_light_fit_workspace_bytes."""
+    chunks = (int(H) * int(W) + LIGHT_FIT_CHUNK - 1) // LIGHT_FIT_CHUNK
+    return LIGHT_FIT_CHUNK, min(chunks, max(1, LIGHT_FIT_MAX_GROUPS // int(B)))
+
+
+def _check_fit(final_shading, albedo, image, weight, image_layout, out=None, shared=False, ridge=0.0):
+    """Every shape, dtype, device and range BEFORE anything is launched or loaded: a mismatch never reaches the kernels."""
+    named = [("final_shading", final_shading), ("albedo", albedo), ("image", image)] \
+        + ([("weight", weight)] if weight is not None else []) + ([("out", out)] if out is not None else [])
+    for n, t in named:
+        if not torch.is_tensor(t):
+            raise _lib.GcfrError("fit_light_rgb: %s must be a tensor, got %s" % (n, type(t).__name__))
+        if t.dtype != torch.float32 and not (n == "weight" and t.dtype == torch.uint8):
+            raise _lib.GcfrError("fit_light_rgb: %s must be float32%s, got %s" % (n, " or uint8" if n == "weight" else "", t.dtype))
+    if any(t.device != final_shading.device for _, t in named):
+        raise _lib.GcfrError("fit_light_rgb: tensors on one device; got %s" % ", ".join(str(t.device) for _, t in named))
+    if image_layout not in ("nhwc", "nchw"):
+        raise _lib.GcfrError("image_layout must be 'nhwc' or 'nchw'; got %r" % (image_layout,))
+    if final_shading.dim() != 4:
+        raise _lib.GcfrError("final_shading must be (B,L,H,W) -- the many-lights form, with its light axis; got %s"
+                             % (tuple(final_shading.shape),))
+    B, L, H, W = final_shading.shape
+    if B < 1 or H < 1 or W < 1 or not 1 <= L <= MAX_FIT_LIGHTS:
+        raise _lib.GcfrError("final_shading (B,L,H,W) = %s: B, H, W >= 1 and 1 <= L <= %d" % (tuple(final_shading.shape), MAX_FIT_LIGHTS))
+    if B > 65535 or H * W >= 2 ** 31 - LIGHT_FIT_CHUNK:
+        raise _lib.GcfrError("final_shading (B,L,H,W) = %s: B <= 65535 and H W < 2^31 - %d" % (tuple(final_shading.shape), LIGHT_FIT_CHUNK))
+    if tuple(albedo.shape) != (B, 3, H, W):
+        raise _lib.GcfrError("albedo must be %s for final_shading %s; got %s" % ((B, 3, H, W), tuple(final_shading.shape), tuple(albedo.shape)))
+    want = (B, H, W, 3) if image_layout == "nhwc" else (B, 3, H, W)
+    if tuple(image.shape) != want:
+        raise _lib.GcfrError("image must be %s (image_layout=%r) for final_shading %s; got %s"
+                             % (want, image_layout, tuple(final_shading.shape), tuple(image.shape)))
+    if weight is not None and tuple(weight.shape) not in ((H, W), (1, H, W), (B, H, W)):
+        raise _lib.GcfrError("weight must be (%d,%d,%d), (1,%d,%d) or (%d,%d); got %s" % (B, H, W, H, W, H, W, tuple(weight.shape)))
+    if not (isinstance(ridge, (int, float)) and math.isfinite(ridge) and ridge >= 0.0):
+        raise _lib.GcfrError("ridge must be a finite number >= 0; got %r" % (ridge,))
+    if out is not None:
+        rigs = 1 if shared else B
+        if tuple(out.shape) != (rigs, L, 3) or not out.is_contiguous():
+            raise _lib.GcfrError("out must be a contiguous (%d,%d,3) tensor; got %s" % (rigs, L, tuple(out.shape)))
+        if out.requires_grad:
+            raise _lib.GcfrError("out must not require a gradient: it is a buffer the result is written into")
+    _lib.require_device(*[t for _, t in named])
+
+
+def _fit_weight(weight):
+    """the weight as the kernel reads it: f32, contiguous, (1|B,H,W); a u8 mask is divided by 255 in f32"""
+    if weight is None:
+        return None
+    w = weight.detach()
+    if w.dtype == torch.uint8:       # an IEEE f32 division: by a device tensor (torch turns a division by a Python scalar into a product)
+        w = w.to(torch.float32) / torch.full((1,), 255.0, dtype=torch.float32, device=w.device)
+    return (w[None] if w.dim() == 2 else w).contiguous()
+
+
+def _launch_fit_normal(final, albedo, image, nhwc, weight, gram, rhs):
+    B, L, H, W = final.shape
+    dev = final.device
+    lib = _lib.load()
+    with torch.cuda.device(dev):
+        ws = torch.empty(max(8, int(lib.gcfr_light_fit_workspace_bytes(B, L, H, W))) // 8, dtype=torch.float64, device=dev)
+        _lib.check(lib.gcfr_light_fit_normal(final.data_ptr(), albedo.data_ptr(), image.data_ptr(), 1 if nhwc else 0, _lib.ptr(weight),
+                                             1 if weight is None else weight.shape[0], B, L, H, W, ws.data_ptr(), gram.data_ptr(),
+                                             rhs.data_ptr(), _lib.stream_ptr(dev)), "gcfr_light_fit_normal")
+
+
+def _launch_fit_solve(gram, rhs, ridge, rgb, info):
+    B, _, L, _ = gram.shape
+    dev = gram.device
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().gcfr_light_fit_solve(gram.data_ptr(), rhs.data_ptr(), B, L, float(ridge), rgb.shape[0], rgb.data_ptr(),
+                                                    info.data_ptr(), _lib.stream_ptr(dev)), "gcfr_light_fit_solve")
+
+
+def _normal_equations(final_shading, albedo, image, weight, image_layout):
+    """light_normal_equations behind its checks"""
+    B, L, _, _ = final_shading.shape
+    dev = final_shading.device
+    gram = torch.empty((B, 3, L, L), dtype=torch.float64, device=dev)
+    rhs = torch.empty((B, 3, L), dtype=torch.float64, device=dev)
+    _launch_fit_normal(final_shading.detach().contiguous(), albedo.detach().contiguous(), image.detach().contiguous(),
+                       image_layout == "nhwc", _fit_weight(weight), gram, rhs)
+    return gram, rhs
+
+
+def light_normal_equations(final_shading: torch.Tensor, albedo: torch.Tensor, image: torch.Tensor, weight=None,
+                           image_layout: str = "nhwc"):
+    """(gram (B,3,L,L) f64, rhs (B,3,L) f64): the normal equations of `fit_light_rgb`, per face b and channel c
+    gram[b,c,l,l'] = sum_p w a_c^2 f_l f_l', rhs[b,c,l] = sum_p w a_c I_c f_l, over the pixels p of `final_shading` (B,L,H,W),
+    `albedo` (B,3,H,W), the photograph `image` ((B,H,W,3) for image_layout "nhwc", (B,3,H,W) for "nchw") and `weight`
+    ((B,H,W), or (1,H,W) / (H,W) shared; f32, or u8 divided by 255 in f32; None: ones).  f64 sums in a fixed order
+    (include/gcfr.h): equal inputs give equal bits; gram is exactly symmetric.  Nothing is clamped; a non-finite value reaches the
+    entries it enters, also under a weight of 0.  1 <= L <= 64.  Not differentiable (inputs are detached); no host
+    synchronisation; a malformed input raises GcfrError before any launch.  There is no CPU path."""
+    _check_fit(final_shading, albedo, image, weight, image_layout)
+    return _normal_equations(final_shading, albedo, image, weight, image_layout)
+
+
+def fit_light_rgb(final_shading: torch.Tensor, albedo: torch.Tensor, image: torch.Tensor, weight=None, ridge: float = 1e-3,
+                  shared: bool = False, image_layout: str = "nhwc", out=None, return_info: bool = False):
+    """The rig `light_rgb` (B,L,3) -- (1,L,3) with `shared=True`, one rig fitted to all faces -- under which `combine_lights`
+    followed by the mask paste comes closest to the photograph `image`: per face and channel the weighted least-squares problem
+        minimise  sum_p w (image_c - albedo_c sum_l x[l,c] final_shading[l])^2  +  ridge (trace(G_c) / L) |x[:,c]|^2
+    with G_c the Gram matrix of `light_normal_equations` (arguments as there).  The ridge is relative to the problem's own scale;
+    `ridge=0` is plain least squares.  Two launches form the normal equations, one solves them by Cholesky factorisation in f64
+    and rounds once to f32; every operation's order is fixed (include/gcfr.h): equal inputs give equal bits.
+    The default `ridge` is a convenience, not a gate: lights close to each other have nearly parallel shadings and make G
+    ill-conditioned, the fit then trades large weights of opposite sign against each other, and the result MAY CONTAIN NEGATIVE
+    ENTRIES.  The rig stage allows them; there is no non-negative solver here.
+    `out`: a contiguous f32 buffer of the result's shape that the result is written into and which is returned --
+    `RelightSession.light_rgb` between two replays, for example: a captured session is re-lit from a photograph without recapture.
+    `return_info=True` returns (light_rgb, info): info (B|1,3) i32 ON THE DEVICE, 0 where the channel was solved, k + 1 where pivot k
+    of the factorisation was not a positive finite number (a singular system: that channel's L entries are NaN).  The function
+    never synchronises with the host, so it cannot raise on a failed solve: look at `info`, or at the NaNs.
+    NOT DIFFERENTIABLE: the inputs are detached and the result carries no graph.  A malformed input (rank, shape, dtype, device,
+    L outside 1 .. 64, layout, `out`) raises GcfrError before anything is loaded or launched; host tensors raise too."""
+    _check_fit(final_shading, albedo, image, weight, image_layout, out, shared, ridge)
+    B, L, _, _ = final_shading.shape
+    dev = final_shading.device
+    gram, rhs = _normal_equations(final_shading, albedo, image, weight, image_layout)
+    rigs = 1 if shared else B
+    rgb = torch.empty((rigs, L, 3), dtype=torch.float32, device=dev) if out is None else out
+    info = torch.empty((rigs, 3), dtype=torch.int32, device=dev)
+    _launch_fit_solve(gram, rhs, ridge, rgb, info)
+    return (rgb, info) if return_info else rgb

@@ -631,6 +631,70 @@ int gcfr_environment_bwd(const float *g_rgb, const double *row_w, const int32_t 
                          float *g_env, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Rig capture: the `rgb` (colour x weight per light) of the light-rig stage above FITTED to a photograph, by weighted least squares
+ * over the per-light shadings of the many-lights path (csrc/gcfr_light_fit.hip).  Per face b and channel c, over the pixels p:
+ *   minimise  sum_p w[b,p] (image[b,c,p] - albedo[b,c,p] sum_l x[b,l,c] final_shading[b,l,p])^2  +  lambda_c |x[b,:,c]|^2
+ * whose normal equations are A_c x_c = r_c with
+ *   G_c[l,l'] = sum_p w a_c^2 f_l f_l'     r_c[l] = sum_p w a_c I_c f_l     A_c = G_c + ridge (trace(G_c) / L) I
+ * gcfr_light_fit_normal forms G and r, gcfr_light_fit_solve solves.  1 <= L <= 64, 1 <= B <= 65535, H, W >= 1 with H W < 2^31 - 64.
+ * The entries allocate nothing, never synchronise, use no floating-point atomic and no cross-lane reduction, and may be captured
+ * into a graph.  Every sum is an f64 sum in a FIXED order, stated below: two calls return the same bits, and the numpy restatement of
+ * that order (tests/light_fit_emulation.py) returns them too.  The library is built with -ffp-contract=off: every product and sum
+ * below is one IEEE f64 operation.
+ * ------------------------------------------------------------------------------------------- */
+
+/*
+ * Bytes of caller-owned scratch gcfr_light_fit_normal needs for its per-workgroup partials: 8 B groups 3 L (L + 3) / 2 with
+ * groups = min(ceil(H W / 64), max(1, 512 / B)), the workgroups per face (a chunk is 64 pixels; 512 workgroups per launch at the
+ * most).  0 for a shape outside the ranges above.
+ */
+size_t gcfr_light_fit_workspace_bytes(int32_t B, int32_t L, int32_t H, int32_t W);
+
+/*
+ * The normal equations, two launches.  All planes contiguous:
+ *   final_shading (B,L,H,W) f32      the many-lights `final`
+ *   albedo        (B,3,H,W) f32
+ *   image         f32                the photograph: (B,H,W,3) when image_nhwc = 1, (B,3,H,W) when image_nhwc = 0
+ *   weight        f32 or NULL        (weight_batch,H,W) with weight_batch = B (per face) or 1 (shared); NULL: all ones
+ *   workspace     gcfr_light_fit_workspace_bytes(B, L, H, W) bytes, 8-byte aligned; its contents afterwards are unspecified
+ *   gram (B,3,L,L) F64 out, rhs (B,3,L) F64 out      8-byte aligned; every element is written once (the caller clears nothing)
+ * A NULL among the required pointers, a misaligned f64 pointer, image_nhwc other than 0 / 1, weight_batch other than 1 / B with a
+ * weight, or a shape out of range is GCFR_ERR_INVALID_ARGUMENT before any launch.
+ * Order of operations, per pixel p and channel c, in f64:
+ *   s = (double)w * (double)a_c          (exact)
+ *   q = s * (double)a_c                  u = s * (double)I_c
+ *   G_c[l,l'] += (q * (double)f_l) * (double)f_l'     for l' <= l
+ *   r_c[l]    += u * (double)f_l
+ * Who sums what: the face's pixels are cut into chunks of 64 consecutive pixels; workgroup g of the face's `groups` takes the chunks
+ * g, g + groups, g + 2 groups, ...  Each entry of a workgroup's partial is summed by ONE lane, sequentially over that workgroup's
+ * pixels in ascending pixel order, starting from +0.  An entry of the face's total is the sum of its workgroups' partials in
+ * ascending workgroup order, starting from partial 0 (no add to zero).  gram is written full and symmetric: the upper triangle is a
+ * copy of the lower one, not a second sum.  Nothing is clamped: non-finite values propagate to the entries they enter, also under
+ * a weight of 0 (0 * NaN is NaN).
+ */
+int gcfr_light_fit_normal(const float *final_shading, const float *albedo, const float *image, int32_t image_nhwc,
+                          const float *weight, int32_t weight_batch, int32_t B, int32_t L, int32_t H, int32_t W, void *workspace,
+                          double *gram, double *rhs, void *stream);
+
+/*
+ * The solve, one launch, one workgroup per (rig, channel):   gram (B,3,L,L) F64, rhs (B,3,L) F64   ->   rgb (rgb_batch,L,3) f32,
+ * the layout gcfr_light_rig_fwd takes, and info (rgb_batch,3) i32.  rgb_batch = B fits a rig per face; rgb_batch = 1 fits ONE rig
+ * to all faces: the B matrices and right-hand sides are added first, entry by entry, in ascending b starting from face 0's.
+ * Only gram's lower triangle is read.  ridge >= 0 and finite, rgb_batch = 1 or B, 1 <= L <= 64, 1 <= B <= 65535, no NULL, f64
+ * pointers 8-byte aligned: anything else is GCFR_ERR_INVALID_ARGUMENT before the launch.  Order, all f64, one lane per sum:
+ *   trace = 0; trace += G[l,l] for l ascending;   A[l,l] = G[l,l] + ridge * (trace / (double)L)       (ridge = 0 adds an exact 0)
+ *   Cholesky, column k ascending:  s_i = A[i,k]; s_i = s_i - C[i,m] * C[k,m] for m = 0 .. k-1 ascending   (every row i >= k);
+ *       the pivot s_k must be a positive finite number; C[k,k] = sqrt(s_k), C[i,k] = s_i / C[k,k]         (IEEE sqrt and division)
+ *   forward, k ascending:   z_k = y_k / C[k,k];  y_i = y_i - C[i,k] * z_k for i > k                    (y starts as the right-hand side)
+ *   back, k descending:     x_k = z_k / C[k,k];  z_i = z_i - C[k,i] * x_k for i < k
+ *   rgb[., l, c] = (float)x_l, one rounding.
+ * info[., c] = 0 on success.  When pivot k is not a positive finite number, info[., c] = k + 1 and that channel's L entries of rgb
+ * are NaN; nothing else is written.  A non-finite right-hand side under a good matrix gives non-finite rgb with info = 0.
+ */
+int gcfr_light_fit_solve(const double *gram, const double *rhs, int32_t B, int32_t L, double ridge, int32_t rgb_batch, float *rgb,
+                         int32_t *info, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Measurement aid (bench.py `roofline.hbm_measured_copy_GBs`): a float4 grid-stride device-to-device copy of `bytes` bytes
  * (multiple of 16, both pointers 16-byte aligned), one workgroup of 256 lanes per CU, four loads in flight per lane, non-temporal --
  * the achievable-HBM probe (6.3 TB/s, read + write) the roofline's 8 TB/s spec peak is reported beside.  Not part of the render path.
