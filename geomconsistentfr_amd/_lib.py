@@ -50,26 +50,25 @@ def options(tile_w=0, group=0, ksplit=-1, depth_bound_skip=-1, event_start=None,
     return o
 
 
-def with_phase(o, phase: int) -> Options:
-    """a copy of `o` (or the defaults) with `phase` set: 1 = the prepass only, 2 = the march only (include/gcfr.h)"""
+def _with(o, field: str, value: int) -> Options:
+    """a copy of `o` (or the defaults) with one field set"""
     n = Options()
     if o is None:
         load().gcfr_options_default(ctypes.byref(n))
     else:
         ctypes.memmove(ctypes.byref(n), ctypes.byref(o), ctypes.sizeof(Options))
-    n.phase = phase
+    setattr(n, field, value)
     return n
+
+
+def with_phase(o, phase: int) -> Options:
+    """a copy of `o` (or the defaults) with `phase` set: 1 = the prepass only, 2 = the march only (include/gcfr.h)"""
+    return _with(o, "phase", phase)
 
 
 def with_pixels(o, pixels: int) -> Options:
     """a copy of `o` (or the defaults) with `pixels` set -- RenderParams(pixels="mask") reaches the library this way"""
-    n = Options()
-    if o is None:
-        load().gcfr_options_default(ctypes.byref(n))
-    else:
-        ctypes.memmove(ctypes.byref(n), ctypes.byref(o), ctypes.sizeof(Options))
-    n.pixels = pixels
-    return n
+    return _with(o, "pixels", pixels)
 
 
 def opt_ref(o):

@@ -4,6 +4,7 @@
 HIP kernels of libgcfr_hip.so; torch is used for device memory, streams and (later) autograd glue.
 All tensors must live on a ROCm device; there is no CPU path.
 """
+import ctypes
 from dataclasses import dataclass
 from typing import Optional, Tuple
 
@@ -127,7 +128,6 @@ def shadow_min_distance(depth: torch.Tensor, mask: torch.Tensor, light_pt: torch
 
 
 def ctypes_float4(v):
-    import ctypes
     arr = (ctypes.c_float * 4)(*[float(x) for x in v])
     return ctypes.cast(arr, ctypes.c_void_p)
 
@@ -206,13 +206,89 @@ def source_signature(*tensors):
 
 
 def _prepass_key(shapes, params, options):
-    import ctypes
     knobs = None
     if options is not None:
         o = _lib.with_phase(options, 0)
         o.event_start = o.event_stop = None
         knobs = bytes(ctypes.string_at(ctypes.byref(o), ctypes.sizeof(o)))
     return (shapes, params, knobs)
+
+
+# The positional argument lists of the three forward entries, by the parameter names of their prototypes in include/gcfr.h
+# (tests/test_block_host.py holds each to its prototype).  Values are addresses and sizes (int), floats, None (NULL) or ctypes
+# objects.  These bodies are the only places where the orders are written down.
+
+def _render_fwd_args(*, light_raw, clamp_z, clamp_min, light_distance, depth, mask_u8, mask_batch, normals, albedo, ambient,
+                     B, L, H, W, N, t_table, bonus, bonus_box, intensity, unit_out, light_pt_out, min_dist, argmin,
+                     shadow_w, full, final_shading, rendered, workspace, workspace_bytes, stream, opt):
+    return (light_raw, clamp_z, clamp_min, light_distance, depth, mask_u8, mask_batch, normals, albedo, ambient,
+            B, L, H, W, N, t_table, bonus, bonus_box, intensity, unit_out, light_pt_out, min_dist, argmin,
+            shadow_w, full, final_shading, rendered, workspace, workspace_bytes, stream, opt)
+
+
+def _render_from_depth_fwd_args(*, light_raw, clamp_z, clamp_min, light_distance, depth, mask_u8, mask_batch, fx, fy, cx, cy,
+                                z_offset, negate_y, albedo, ambient, B, L, H, W, N, t_table, bonus, bonus_box, intensity,
+                                unit_out, light_pt_out, min_dist, argmin, normals_out, shadow_w, full, final_shading,
+                                rendered, workspace, workspace_bytes, stream, opt):
+    return (light_raw, clamp_z, clamp_min, light_distance, depth, mask_u8, mask_batch, fx, fy, cx, cy,
+            z_offset, negate_y, albedo, ambient, B, L, H, W, N, t_table, bonus, bonus_box, intensity,
+            unit_out, light_pt_out, min_dist, argmin, normals_out, shadow_w, full, final_shading,
+            rendered, workspace, workspace_bytes, stream, opt)
+
+
+def _normals_fwd_args(*, depth, B, H, W, fx, fy, cx, cy, z_offset, negate_y, normals, stream):
+    return (depth, B, H, W, fx, fy, cx, cy, z_offset, negate_y, normals, stream)
+
+
+class _Forward:
+    """The forward's launches for one (params, B, L, H, W, device, camera, normals stage): holds the keywords that no call
+    changes.  `bind()` adds one set of buffers (once per set: RenderFwdPlan keeps the result); the stream and the options
+    of a call travel in two pointer cells of the object's own, which every bound list holds and the call sets.
+    camera=None: gcfr_render_fwd on normals handed in (the prepass is this form at phase 1, the operands it does not have
+    left None); "kernel": gcfr_normals_fwd, then gcfr_render_fwd on its output; "fused": gcfr_render_from_depth_fwd."""
+
+    def __init__(self, params, B, L, H, W, dev, camera=None, stage="fused"):
+        self.L_ = _lib.load()
+        self.form = "given" if camera is None else stage
+        self.table = sample_table(params, dev)
+        self.stream, self.opt = ctypes.c_void_p(), ctypes.c_void_p()
+        self.const = dict(clamp_z=int(params.clamp_light_z_min is not None), clamp_min=float(params.clamp_light_z_min or 0.0),
+                          light_distance=float(params.light_distance), B=B, L=L, H=H, W=W, N=params.n_samples,
+                          t_table=self.table.data_ptr(), bonus=float(params.inside_bonus),
+                          bonus_box=ctypes_float4(params.bonus_box) if params.bonus_box is not None else None,
+                          intensity=float(params.directional_intensity), stream=self.stream, opt=self.opt)
+        if camera is not None:
+            fx, fy, cx, cy, z_off = [float(v) for v in camera]
+            self.cam = dict(fx=fx, fy=fy, cx=cx, cy=cy, z_offset=z_off, negate_y=1)
+
+    def bind(self, light, depth, mask_u8, mask_batch, normals, albedo, ambient, out, ws, ws_bytes):
+        """(normals launch | None, march launch) for these tensors (None = NULL; `out`: the outputs by `render_fwd`'s names,
+        an absent one is NULL); the tensors have to outlive the launches"""
+        p = _lib.ptr
+        kw = dict(self.const, light_raw=p(light), depth=p(depth), mask_u8=p(mask_u8), mask_batch=mask_batch, albedo=p(albedo),
+                  ambient=p(ambient), unit_out=p(out["unit_light_direction"]), light_pt_out=p(out["light_pt"]),
+                  min_dist=p(out.get("minimum_distance")), argmin=p(out.get("argmin")), shadow_w=p(out.get("shadow_mask_weights")),
+                  full=p(out.get("full_shading")), final_shading=p(out.get("final_shading")), rendered=p(out.get("rendered_images")),
+                  workspace=p(ws), workspace_bytes=ws_bytes)
+        if self.form == "given":
+            return None, _render_fwd_args(normals=p(normals), **kw)
+        nrm = p(out["surface_normals"])
+        if self.form == "fused":
+            return None, _render_from_depth_fwd_args(normals_out=nrm, **self.cam, **kw)
+        return (_normals_fwd_args(depth=kw["depth"], B=kw["B"], H=kw["H"], W=kw["W"], normals=nrm, stream=self.stream, **self.cam),
+                _render_fwd_args(normals=nrm, **kw))
+
+    def __call__(self, bound, stream, options, phase=0, what=""):
+        """enqueue the form's launches on `stream` (phase: gcfr_options.phase; the normals launch belongs to the march)"""
+        normals, march = bound
+        o = options if phase == 0 else _lib.with_phase(options, phase)
+        self.stream.value, self.opt.value = stream, (None if o is None else ctypes.addressof(o))
+        if self.form == "fused":
+            _lib.check(self.L_.gcfr_render_from_depth_fwd(*march), "gcfr_render_from_depth_fwd" + what)
+            return
+        if normals is not None and phase != 1:
+            _lib.check(self.L_.gcfr_normals_fwd(*normals), "gcfr_normals_fwd" + what)
+        _lib.check(self.L_.gcfr_render_fwd(*march), "gcfr_render_fwd" + what)
 
 
 def render_prepass(depth, mask, light, params: RenderParams = RenderParams(), want_argmin: bool = True, options=None,
@@ -238,7 +314,7 @@ def render_prepass(depth, mask, light, params: RenderParams = RenderParams(), wa
     mask_u8 = mask_to_u8(mask).reshape(-1, H, W)
     light = _f32c(light).reshape(B, -1, 3)
     L = light.shape[1]
-    tt = sample_table(params, dev)
+    fwd = _Forward(params, B, L, H, W, dev)
     p = Prepared()
     p.depth, p.mask_u8, p.light = depth, mask_u8, light          # (kept alive until the march has been enqueued)
     p.unit = torch.empty((B, L, 3), dtype=torch.float32, device=dev)
@@ -247,20 +323,14 @@ def render_prepass(depth, mask, light, params: RenderParams = RenderParams(), wa
     p.ws = torch.empty(p.ws_bytes, dtype=torch.uint8, device=dev)
     p.src = src
     p.key = _prepass_key((tuple(depth.shape), tuple(mask_u8.shape), tuple(light.shape)), params, options)
-    box = ctypes_float4(params.bonus_box) if params.bonus_box is not None else None
-    clamp = params.clamp_light_z_min is not None
     side = stream if stream is not None else side_stream(dev)
     side.wait_stream(torch.cuda.current_stream(dev))              # depth / light are produced on the current stream
     for t in (depth, mask_u8, light, p.unit, p.pt, p.ws):         # allocated on the current stream, used on `side`: the
         t.record_stream(side)                                     # caching allocator must not recycle them under the prepass
-    opt1 = _lib.with_phase(options, 1)
+    bound = fwd.bind(light, depth, mask_u8, mask_u8.shape[0], None, None, None,
+                     dict(unit_light_direction=p.unit, light_pt=p.pt), p.ws, p.ws_bytes)
     with torch.cuda.device(dev), torch.cuda.stream(side):
-        _lib.check(L_.gcfr_render_fwd(
-            light.data_ptr(), int(clamp), float(params.clamp_light_z_min or 0.0), float(params.light_distance),
-            depth.data_ptr(), mask_u8.data_ptr(), mask_u8.shape[0], None, None, None, B, L, H, W, params.n_samples,
-            tt.data_ptr(), float(params.inside_bonus), box, float(params.directional_intensity), p.unit.data_ptr(),
-            p.pt.data_ptr(), None, None, None, None, None, None, p.ws.data_ptr(), p.ws_bytes, side.cuda_stream,
-            _lib.opt_ref(opt1)), "gcfr_render_fwd (prepass)")
+        fwd(bound, side.cuda_stream, options, 1, " (prepass)")
         p.event = torch.cuda.Event()
         p.event.record(side)
     return p
@@ -282,7 +352,6 @@ def render_fwd(depth, mask, light, ambient, normals, albedo, params: RenderParam
     if normals is None and camera is None:
         raise _lib.GcfrError("render_fwd needs either normals or camera=(fx, fy, cx, cy, z_offset)")
     want_argmin, options = _pixels_options(params, want_argmin, options)
-    L_ = _lib.load()
     if prepared is not None:
         # the march reads the very tensors the prepass read (its f32 / u8 copies where the caller's were converted): what the
         # caller hands over NOW must be what it handed to the prepass, unmodified
@@ -307,63 +376,37 @@ def render_fwd(depth, mask, light, ambient, normals, albedo, params: RenderParam
         _require_device(normals)
         normals = _f32c(normals).reshape(B, 3, H, W)
     albedo = _f32c(albedo).reshape(B, 3, H, W)
-    tt = sample_table(params, dev)
+    # from NORMALS_KERNEL_MIN_LIGHTS lights per face: the light-independent stencil once, in its own launch, instead of once
+    # per light in the march's epilogue (the same bits)
+    fwd = _Forward(params, B, L, H, W, dev, camera if normals is None else None, normals_stage_for(L))
+    out, ws, ws_bytes = _alloc_forward(B, L, H, W, dev, want_argmin, normals is None, prepared)
+    if prepared is not None:
+        torch.cuda.current_stream(dev).wait_event(prepared.event)     # the march starts behind the prepass
+    bound = fwd.bind(light, depth, mask_u8, mask_u8.shape[0], normals, albedo, ambient, out, ws, ws_bytes)
+    with torch.cuda.device(dev):
+        fwd(bound, _stream_ptr(dev), options, 0 if prepared is None else 2)
+    return out
+
+
+def _alloc_forward(B, L, H, W, dev, want_argmin, normals_out, prepared=None):
+    """(the forward's outputs by name, its workspace, the workspace's size), freshly allocated; with `prepared` the light
+    outputs and the workspace are the ones the prepass wrote"""
     f32 = dict(dtype=torch.float32, device=dev)
     md = torch.empty((B, L, H, W), **f32)
     am = torch.empty((B, L, H, W), dtype=torch.int32, device=dev) if want_argmin else None
-    w = torch.empty((B, L, H, W), **f32)
-    full = torch.empty((B, L, H, W), **f32)
-    fin = torch.empty((B, L, H, W), **f32)
+    w, full, fin = [torch.empty((B, L, H, W), **f32) for _ in range(3)]
     ren = torch.empty((B, L, 3, H, W), **f32)
     if prepared is None:
-        unit = torch.empty((B, L, 3), **f32)
-        pt = torch.empty((B, L, 3), **f32)
-        ws_bytes = int(L_.gcfr_shadow_workspace_bytes(B, H, W))
+        unit, pt = torch.empty((B, L, 3), **f32), torch.empty((B, L, 3), **f32)
+        ws_bytes = int(_lib.load().gcfr_shadow_workspace_bytes(B, H, W))
         ws = torch.empty(ws_bytes, dtype=torch.uint8, device=dev)
     else:
         unit, pt, ws, ws_bytes = prepared.unit, prepared.pt, prepared.ws, prepared.ws_bytes
-        torch.cuda.current_stream(dev).wait_event(prepared.event)     # the march starts behind the prepass
-        options = _lib.with_phase(options, 2)
-    box = ctypes_float4(params.bonus_box) if params.bonus_box is not None else None
-    clamp = params.clamp_light_z_min is not None
     out = dict(unit_light_direction=unit, light_pt=pt, minimum_distance=md, argmin=am, shadow_mask_weights=w,
                full_shading=full, final_shading=fin, rendered_images=ren)
-    with torch.cuda.device(dev):
-        if normals is not None:
-            _lib.check(L_.gcfr_render_fwd(
-                light.data_ptr(), int(clamp), float(params.clamp_light_z_min or 0.0), float(params.light_distance),
-                depth.data_ptr(), mask_u8.data_ptr(), mask_u8.shape[0], normals.data_ptr(), albedo.data_ptr(),
-                ambient.data_ptr(), B, L, H, W, params.n_samples, tt.data_ptr(), float(params.inside_bonus), box,
-                float(params.directional_intensity), unit.data_ptr(), pt.data_ptr(), md.data_ptr(), _opt_ptr(am),
-                w.data_ptr(), full.data_ptr(), fin.data_ptr(), ren.data_ptr(), ws.data_ptr(), ws_bytes,
-                _stream_ptr(dev), _lib.opt_ref(options)), "gcfr_render_fwd")
-        elif normals_stage_for(L) == "kernel":
-            # many lights per face: the light-independent stencil once, in its own launch, instead of once per light in the
-            # march's epilogue (the same bits; NORMALS_KERNEL_MIN_LIGHTS)
-            fx, fy, cx, cy, z_off = [float(v) for v in camera]
-            nout = torch.empty((B, 3, H, W), **f32)
-            _lib.check(L_.gcfr_normals_fwd(depth.data_ptr(), B, H, W, fx, fy, cx, cy, z_off, 1, nout.data_ptr(), _stream_ptr(dev)),
-                       "gcfr_normals_fwd")
-            _lib.check(L_.gcfr_render_fwd(
-                light.data_ptr(), int(clamp), float(params.clamp_light_z_min or 0.0), float(params.light_distance),
-                depth.data_ptr(), mask_u8.data_ptr(), mask_u8.shape[0], nout.data_ptr(), albedo.data_ptr(),
-                ambient.data_ptr(), B, L, H, W, params.n_samples, tt.data_ptr(), float(params.inside_bonus), box,
-                float(params.directional_intensity), unit.data_ptr(), pt.data_ptr(), md.data_ptr(), _opt_ptr(am),
-                w.data_ptr(), full.data_ptr(), fin.data_ptr(), ren.data_ptr(), ws.data_ptr(), ws_bytes,
-                _stream_ptr(dev), _lib.opt_ref(options)), "gcfr_render_fwd")
-            out["surface_normals"] = nout
-        else:
-            fx, fy, cx, cy, z_off = [float(v) for v in camera]
-            nout = torch.empty((B, 3, H, W), **f32)
-            _lib.check(L_.gcfr_render_from_depth_fwd(
-                light.data_ptr(), int(clamp), float(params.clamp_light_z_min or 0.0), float(params.light_distance),
-                depth.data_ptr(), mask_u8.data_ptr(), mask_u8.shape[0], fx, fy, cx, cy, z_off, 1, albedo.data_ptr(),
-                ambient.data_ptr(), B, L, H, W, params.n_samples, tt.data_ptr(), float(params.inside_bonus), box,
-                float(params.directional_intensity), unit.data_ptr(), pt.data_ptr(), md.data_ptr(), _opt_ptr(am),
-                nout.data_ptr(), w.data_ptr(), full.data_ptr(), fin.data_ptr(), ren.data_ptr(), ws.data_ptr(),
-                ws_bytes, _stream_ptr(dev), _lib.opt_ref(options)), "gcfr_render_from_depth_fwd")
-            out["surface_normals"] = nout
-    return out
+    if normals_out:
+        out["surface_normals"] = torch.empty((B, 3, H, W), **f32)
+    return out, ws, ws_bytes
 
 
 def _pixels_options(params: RenderParams, want_argmin: bool, options):
@@ -374,14 +417,6 @@ def _pixels_options(params: RenderParams, want_argmin: bool, options):
     if params.pixels != "mask":
         raise _lib.GcfrError("RenderParams.pixels must be 'all' or 'mask', got %r" % (params.pixels,))
     return True, _lib.with_pixels(options, 1)
-
-
-def _zeros(shape, dtype, device):
-    return torch.zeros(shape, dtype=dtype, device=device)
-
-
-def _opt_ptr(t):
-    return t.data_ptr() if t is not None else None
 
 
 def _light_shapes(B, light, ambient):
@@ -452,29 +487,36 @@ class _RenderFunction(torch.autograd.Function):
         gw, gfull, gfin, gren = [None if g is None else _f32c(g) for g in (g_w, g_full, g_fin, g_ren)]
         grad_normals = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
         grad_albedo = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
-        grad_depth = _zeros((B, H, W), torch.float32, dev)
-        grad_pt = _zeros((B, L, 3), torch.float64, dev)
-        grad_amb = _zeros((B, L), torch.float64, dev)
+        grad_depth = torch.zeros((B, H, W), dtype=torch.float32, device=dev)
+        grad_pt = torch.zeros((B, L, 3), dtype=torch.float64, device=dev)
+        grad_amb = torch.zeros((B, L), dtype=torch.float64, device=dev)
         grad_md = torch.empty((B, L, H, W), dtype=torch.float32, device=dev)
         tt = sample_table(prm, dev)
         with torch.cuda.device(dev):
             st = _stream_ptr(dev)
             _lib.check(L_.gcfr_shade_bwd(normals.data_ptr(), depth3.data_ptr(), albedo.data_ptr(), pt.data_ptr(),
                                          amb.data_ptr(), md.data_ptr(), B, L, H, W, float(prm.directional_intensity),
-                                         _opt_ptr(gw), _opt_ptr(gfull), _opt_ptr(gfin), _opt_ptr(gren),
+                                         _lib.ptr(gw), _lib.ptr(gfull), _lib.ptr(gfin), _lib.ptr(gren),
                                          grad_normals.data_ptr(), grad_albedo.data_ptr(), grad_depth.data_ptr(),
                                          grad_pt.data_ptr(), grad_amb.data_ptr(), grad_md.data_ptr(), st),
                        "gcfr_shade_bwd")
             _lib.check(L_.gcfr_shadow_bwd(grad_md.data_ptr(), depth3.data_ptr(), pt.data_ptr(), am.data_ptr(),
                                           B, L, H, W, prm.n_samples, tt.data_ptr(), grad_depth.data_ptr(),
                                           grad_pt.data_ptr(), st), "gcfr_shadow_bwd")
-            grad_light = torch.empty((B, L, 3), dtype=torch.float32, device=dev)
-            gu = None if g_unit is None else _f32c(g_unit).reshape(B * L, 3)
-            clamp = prm.clamp_light_z_min is not None
-            _lib.check(L_.gcfr_light_prep_bwd(light3.data_ptr(), B * L, int(clamp), float(prm.clamp_light_z_min or 0.0),
-                                              float(prm.light_distance), _opt_ptr(gu), grad_pt.data_ptr(),
-                                              grad_light.data_ptr(), st), "gcfr_light_prep_bwd")
+            grad_light = _light_prep_bwd(light3, g_unit, grad_pt, prm, st)
         return (grad_depth.reshape(B, 1, H, W), grad_albedo, grad_light, grad_amb.float(), grad_normals, None, None)
+
+
+def _light_prep_bwd(light3, g_unit, grad_pt, prm, st):
+    """gcfr_light_prep_bwd on stream `st`: the gradients of the unit direction (g_unit, any shape of B*L*3 elements, or None)
+    and of the light point (grad_pt (B,L,3) f64) -> the raw light's, (B,L,3) f32"""
+    B, L, _ = light3.shape
+    grad_light = torch.empty((B, L, 3), dtype=torch.float32, device=light3.device)
+    gu = None if g_unit is None else _f32c(g_unit).reshape(B * L, 3)
+    _lib.check(_lib.load().gcfr_light_prep_bwd(light3.data_ptr(), B * L, int(prm.clamp_light_z_min is not None),
+                                               float(prm.clamp_light_z_min or 0.0), float(prm.light_distance), _lib.ptr(gu),
+                                               grad_pt.data_ptr(), grad_light.data_ptr(), st), "gcfr_light_prep_bwd")
+    return grad_light
 
 
 def render(depth, albedo, light, ambient, normals, mask, params: RenderParams = RenderParams()):
@@ -507,7 +549,7 @@ class RenderFwdPlan:
 
     def __init__(self, B, L, H, W, params: RenderParams = RenderParams(), device="cuda", want_argmin=False,
                  mask_batch=None, camera=None, options=None, normals_stage="auto"):
-        self.L_ = _lib.load()
+        _lib.load()
         want_argmin, options = _pixels_options(params, want_argmin, options)
         self.options = options          # _lib.Options or None; kept alive here, read by the library at every call
         dev = torch.device(device)
@@ -520,29 +562,10 @@ class RenderFwdPlan:
         # "kernel": gcfr_normals_fwd first, then gcfr_render_fwd reads its output (three launches; the same bits);
         # "auto": by the number of lights per face (normals_stage_for)
         self.normals_stage = normals_stage_for(L, normals_stage)
-        f32 = dict(dtype=torch.float32, device=dev)
-        self.tt = sample_table(params, dev)
-        o = dict(unit_light_direction=torch.empty((B, L, 3), **f32), light_pt=torch.empty((B, L, 3), **f32),
-                 minimum_distance=torch.empty((B, L, H, W), **f32),
-                 argmin=torch.empty((B, L, H, W), dtype=torch.int32, device=dev) if want_argmin else None,
-                 shadow_mask_weights=torch.empty((B, L, H, W), **f32), full_shading=torch.empty((B, L, H, W), **f32),
-                 final_shading=torch.empty((B, L, H, W), **f32), rendered_images=torch.empty((B, L, 3, H, W), **f32))
-        if camera is not None:
-            o["surface_normals"] = torch.empty((B, 3, H, W), **f32)
-        self.out = o
-        self.ws_bytes = int(self.L_.gcfr_shadow_workspace_bytes(B, H, W))
-        self.ws = torch.empty(self.ws_bytes, dtype=torch.uint8, device=dev)
-        self.box = ctypes_float4(params.bonus_box) if params.bonus_box is not None else None
+        self._fwd = _Forward(params, B, L, H, W, dev, camera, self.normals_stage)
+        self.out, self.ws, self.ws_bytes = _alloc_forward(B, L, H, W, dev, want_argmin, camera is not None)
         self.mask_batch = B if mask_batch is None else mask_batch
-        self._tail = (B, L, H, W, params.n_samples, self.tt.data_ptr(), float(params.inside_bonus), self.box,
-                      float(params.directional_intensity), o["unit_light_direction"].data_ptr(),
-                      o["light_pt"].data_ptr(), o["minimum_distance"].data_ptr(), _opt_ptr(o["argmin"]))
-        self._outs = (o["shadow_mask_weights"].data_ptr(), o["full_shading"].data_ptr(),
-                      o["final_shading"].data_ptr(), o["rendered_images"].data_ptr(), self.ws.data_ptr(),
-                      self.ws_bytes)
-        self._head = (int(params.clamp_light_z_min is not None), float(params.clamp_light_z_min or 0.0),
-                      float(params.light_distance))
-        self._validated = None
+        self._validated = self._bound = None    # the buffers of the last call and the launches' argument lists for them
         self.graph = None
 
     def _validate(self, depth, mask_u8, light, ambient, normals, albedo):
@@ -555,18 +578,23 @@ class RenderFwdPlan:
                 raise _lib.GcfrError("RenderFwdPlan: %s must be a contiguous %s tensor of %d elements on %s"
                                      % (name, dt, n, self.dev))
 
+    def _warm_up(self, *static):
+        """keep the (static) input tensors of a capture and run one call on them on a side stream, outside the capture, as
+        torch requires"""
+        self._static = static
+        side = torch.cuda.Stream(device=self.dev)
+        side.wait_stream(torch.cuda.current_stream(self.dev))
+        with torch.cuda.stream(side):
+            self(*static)
+        torch.cuda.current_stream(self.dev).wait_stream(side)
+        torch.cuda.synchronize(self.dev)
+
     def capture(self, depth, mask_u8, light, ambient, normals, albedo):
         """Capture one call on these (static) input tensors into a hipGraph; `replay()` then re-runs it on the
         current stream for ~10 us of host time instead of ~55 (two kernel launches, marshalling 31 arguments).
         The entry points neither allocate nor synchronise, so they are capture-safe.  New data goes into the same
         input tensors (copy_) before a replay."""
-        self._static = (depth, mask_u8, light, ambient, normals, albedo)
-        side = torch.cuda.Stream(device=self.dev)
-        side.wait_stream(torch.cuda.current_stream(self.dev))
-        with torch.cuda.stream(side):                      # warm-up outside the capture, as torch requires
-            self(*self._static)
-        torch.cuda.current_stream(self.dev).wait_stream(side)
-        torch.cuda.synchronize(self.dev)
+        self._warm_up(depth, mask_u8, light, ambient, normals, albedo)
         self.graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph):
             self(*self._static)
@@ -580,13 +608,7 @@ class RenderFwdPlan:
         """The two launches as two hipGraphs (gcfr_options.phase 1 / 2): `replay_prepass()` -- on whatever stream is current,
         typically a side stream, as soon as depth, mask and light are in the captured tensors -- and `replay_march()` behind it
         (the caller orders the two: same stream or an event).  The same bits as `replay()`."""
-        self._static = (depth, mask_u8, light, ambient, normals, albedo)
-        side = torch.cuda.Stream(device=self.dev)
-        side.wait_stream(torch.cuda.current_stream(self.dev))
-        with torch.cuda.stream(side):
-            self(*self._static)
-        torch.cuda.current_stream(self.dev).wait_stream(side)
-        torch.cuda.synchronize(self.dev)
+        self._warm_up(depth, mask_u8, light, ambient, normals, albedo)
         self.graph_pre, self.graph_march = torch.cuda.CUDAGraph(), torch.cuda.CUDAGraph()
         with torch.cuda.graph(self.graph_pre):
             self(*self._static, phase=1)
@@ -612,30 +634,10 @@ class RenderFwdPlan:
                     for t in (depth, mask_u8, light, ambient, normals, albedo))
         if key != self._validated:
             self._validate(depth, mask_u8, light, ambient, normals, albedo)
+            self._bound = self._fwd.bind(light, depth, mask_u8, self.mask_batch, normals, albedo, ambient, self.out, self.ws,
+                                         self.ws_bytes)
             self._validated = key
-        st = torch.cuda.current_stream(self.dev).cuda_stream
-        opts = self.options if phase == 0 else _lib.with_phase(self.options, phase)
-        if self.camera is None:
-            rc = self.L_.gcfr_render_fwd(light.data_ptr(), *self._head, depth.data_ptr(), mask_u8.data_ptr(),
-                                         self.mask_batch, normals.data_ptr(), albedo.data_ptr(), ambient.data_ptr(),
-                                         *self._tail, *self._outs, st, _lib.opt_ref(opts))
-        elif self.normals_stage == "kernel":
-            fx, fy, cx, cy, z_off = [float(v) for v in self.camera]
-            nrm = self.out["surface_normals"]
-            if phase != 1:
-                _lib.check(self.L_.gcfr_normals_fwd(depth.data_ptr(), self.shape[0], self.shape[2], self.shape[3], fx, fy, cx, cy, z_off, 1,
-                                                    nrm.data_ptr(), st), "gcfr_normals_fwd (plan)")
-            rc = self.L_.gcfr_render_fwd(light.data_ptr(), *self._head, depth.data_ptr(), mask_u8.data_ptr(),
-                                         self.mask_batch, nrm.data_ptr(), albedo.data_ptr(), ambient.data_ptr(),
-                                         *self._tail, *self._outs, st, _lib.opt_ref(opts))
-        else:
-            fx, fy, cx, cy, z_off = [float(v) for v in self.camera]
-            rc = self.L_.gcfr_render_from_depth_fwd(light.data_ptr(), *self._head, depth.data_ptr(),
-                                                    mask_u8.data_ptr(), self.mask_batch, fx, fy, cx, cy, z_off, 1,
-                                                    albedo.data_ptr(), ambient.data_ptr(), *self._tail,
-                                                    self.out["surface_normals"].data_ptr(), *self._outs, st,
-                                                    _lib.opt_ref(opts))
-        _lib.check(rc, "gcfr_render_fwd (plan)")
+        self._fwd(self._bound, torch.cuda.current_stream(self.dev).cuda_stream, self.options, phase, " (plan)")
         return self.out
 
 
@@ -679,10 +681,9 @@ class _RenderFromDepthFunction(torch.autograd.Function):
         dev = depth3.device
         gw, gfull, gfin, gren, gnrm = [None if g is None else _f32c(g) for g in (g_w, g_full, g_fin, g_ren, g_nrm)]
         grad_albedo = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
-        grad_depth = _zeros((B, H, W), torch.float32, dev)
-        grad_pt = _zeros((B, L, 3), torch.float64, dev)
-        grad_amb = _zeros((B, L), torch.float64, dev)
-        grad_light = torch.empty((B, L, 3), dtype=torch.float32, device=dev)
+        grad_depth = torch.zeros((B, H, W), dtype=torch.float32, device=dev)
+        grad_pt = torch.zeros((B, L, 3), dtype=torch.float64, device=dev)
+        grad_amb = torch.zeros((B, L), dtype=torch.float64, device=dev)
         tt = sample_table(prm, dev)
         fx, fy, cx, cy, z_off = cam
         with torch.cuda.device(dev):
@@ -691,14 +692,10 @@ class _RenderFromDepthFunction(torch.autograd.Function):
                                           md.data_ptr(), am.data_ptr(), nrm_fwd.data_ptr(), B, L, H, W, prm.n_samples,
                                           tt.data_ptr(),
                                           fx, fy, cx, cy, z_off, 1, float(prm.directional_intensity),
-                                          _opt_ptr(gw), _opt_ptr(gfull), _opt_ptr(gfin), _opt_ptr(gren), _opt_ptr(gnrm),
+                                          _lib.ptr(gw), _lib.ptr(gfull), _lib.ptr(gfin), _lib.ptr(gren), _lib.ptr(gnrm),
                                           grad_albedo.data_ptr(), grad_depth.data_ptr(), grad_pt.data_ptr(),
                                           grad_amb.data_ptr(), st), "gcfr_render_bwd")
-            gu = None if g_unit is None else _f32c(g_unit).reshape(B * L, 3)
-            clamp = prm.clamp_light_z_min is not None
-            _lib.check(L_.gcfr_light_prep_bwd(light3.data_ptr(), B * L, int(clamp), float(prm.clamp_light_z_min or 0.0),
-                                              float(prm.light_distance), _opt_ptr(gu), grad_pt.data_ptr(),
-                                              grad_light.data_ptr(), st), "gcfr_light_prep_bwd")
+            grad_light = _light_prep_bwd(light3, g_unit, grad_pt, prm, st)
         return (grad_depth.reshape(B, 1, H, W), grad_albedo, grad_light, grad_amb.float(), None, None, None, None, None)
 
 

@@ -16,6 +16,9 @@ import numpy as np
 import torch
 
 from . import postprocess as pp
+from ._lib import GcfrError
+from .lighting import (MAX_FIT_LIGHTS, _check_environment, _environment_lights, combine_lights, environment_lights, fit_light_rgb,
+                       sphere_directions)
 from .relightnet import RelightNetLightingTransfer, RelightNetSingleImage
 
 # name -> (x, y, z), test_relight_single_image.py:519-562
@@ -45,6 +48,21 @@ def camera_matrix(focal: float, H: int = 256, W: int = 256, device="cpu") -> tor
 
 def _is_transfer(model) -> bool:
     return isinstance(model, RelightNetLightingTransfer)
+
+
+def _default_focal(transfer: bool, focal):
+    """the scripts' focal length for the model kind (S1:566: 1570; SLT:528: 700) unless the caller gives one"""
+    return (700.0 if transfer else 1570.0) if focal is None else focal
+
+
+def _as_u8(m, device) -> torch.Tensor:
+    return (m if torch.is_tensor(m) else torch.as_tensor(np.asarray(m))).to(device=device, dtype=torch.uint8)
+
+
+def _as_lights(lights, device) -> torch.Tensor:
+    """light directions as an f32 device tensor (L,3) | (B,L,3)"""
+    t = (lights if torch.is_tensor(lights) else torch.as_tensor(np.asarray(lights, np.float32))).to(device=device, dtype=torch.float32)
+    return t.reshape(-1, 3) if t.dim() <= 2 else t
 
 
 def _as_batch(images) -> torch.Tensor:
@@ -107,19 +125,10 @@ def relight_lights_device(model, images, mask_u8, lights, ambient: float = 0.5, 
     """`relight_lights` up to the bytes ON THE DEVICE: (B,L,H,W,3) uint8 tensor, nothing copied back.  `images` / `mask_u8` /
     `lights` may already be device tensors (then nothing is uploaded either): what bench.py's `relight_e2e` leg times."""
     x = _as_batch(images).to(device)
-    B, H, W, _ = x.shape
-    transfer = _is_transfer(model)
-    K = camera_matrix((700.0 if transfer else 1570.0) if focal is None else focal, H, W)          # host: read without a sync
-    as_u8 = lambda m: (m if torch.is_tensor(m) else torch.as_tensor(np.asarray(m))).to(device=device, dtype=torch.uint8)
-    m_u8 = as_u8(mask_u8)
-    mask = (m_u8.to(torch.float64).reshape(H, W, 1) / 255.0)                                                     # S1:580 / SLT:540
-    lights = (lights if torch.is_tensor(lights) else torch.as_tensor(np.asarray(lights, np.float32))).to(device=device, dtype=torch.float32)
-    lights = lights.reshape(-1, 3) if lights.dim() <= 2 else lights
-    out = model.forward_lights(x, epoch, K, mask, lights, float(ambient)) if transfer else model.forward_lights(x, epoch, K, mask, lights)
-    cm = m_u8 if composite_mask_u8 is None else as_u8(composite_mask_u8)
+    out, cm, transfer = _lights_pass(model, x, mask_u8, lights, ambient, focal, device, composite_mask_u8, epoch)
     imgs = pp.inference_images_device(x, out[5], cm, mask_f32=transfer)["rendered_image"]                        # (B,L,H,W,3)
     if fix_border:
-        L = imgs.shape[1]
+        B, L, H, W, _ = imgs.shape
         imgs = pp.fix_border_artifacts_device(imgs.reshape(B * L, H, W, 3), cm).reshape(B, L, H, W, 3)
     return imgs
 
@@ -146,7 +155,6 @@ def _as_light_rgb(light_rgb, device) -> torch.Tensor:
 def _rig_composites(x, out, cm, light_rgb, transfer: bool, fix_border: bool) -> torch.Tensor:
     """`forward_lights`' tuple -> (B,H,W,3) uint8: the rig stage on its albedo (out[0]) and final shading (out[8]), then the image
     kernel at one image per photograph and the optional border fix"""
-    from .lighting import combine_lights
     rendered, _ = combine_lights(out[8], out[0], light_rgb)
     imgs = pp.inference_images_device(x, rendered, cm, mask_f32=transfer)["rendered_image"]
     return pp.fix_border_artifacts_device(imgs, cm) if fix_border else imgs
@@ -158,16 +166,7 @@ def relight_rig_device(model, images, mask_u8, lights, light_rgb, ambient: float
     """`relight_rig` up to the bytes ON THE DEVICE: (B,H,W,3) uint8 tensor, nothing copied back.  `images` / `mask_u8` / `lights` /
     `light_rgb` may already be device tensors."""
     x = _as_batch(images).to(device)
-    B, H, W, _ = x.shape
-    transfer = _is_transfer(model)
-    K = camera_matrix((700.0 if transfer else 1570.0) if focal is None else focal, H, W)          # host: read without a sync
-    as_u8 = lambda m: (m if torch.is_tensor(m) else torch.as_tensor(np.asarray(m))).to(device=device, dtype=torch.uint8)
-    m_u8 = as_u8(mask_u8)
-    mask = (m_u8.to(torch.float64).reshape(H, W, 1) / 255.0)                                                     # S1:580 / SLT:540
-    lights = (lights if torch.is_tensor(lights) else torch.as_tensor(np.asarray(lights, np.float32))).to(device=device, dtype=torch.float32)
-    lights = lights.reshape(-1, 3) if lights.dim() <= 2 else lights
-    out = model.forward_lights(x, epoch, K, mask, lights, float(ambient)) if transfer else model.forward_lights(x, epoch, K, mask, lights)
-    cm = m_u8 if composite_mask_u8 is None else as_u8(composite_mask_u8)
+    out, cm, transfer = _lights_pass(model, x, mask_u8, lights, ambient, focal, device, composite_mask_u8, epoch)
     return _rig_composites(x, out, cm, _as_light_rgb(light_rgb, x.device), transfer, fix_border)
 
 
@@ -191,25 +190,22 @@ def _as_environment(env, device) -> torch.Tensor:
 
 
 def _environment_directions(n_lights, min_z, device) -> torch.Tensor:
-    from .lighting import sphere_directions
     return torch.from_numpy(sphere_directions(n_lights, min_z)).to(device)
 
 
 def _lights_pass(model, x, mask_u8, lights, ambient, focal, device, composite_mask_u8, epoch):
-    """ONE `forward_lights` pass of `x` (B,H,W,3, on the device) under `lights` (L,3) | (B,L,3), exactly as `relight_rig_device`
-    runs it (keep the two in step: the environment entries are held byte for byte to `relight_rig_device`).  Returns three values:
+    """ONE `forward_lights` pass of `x` (B,H,W,3, on the device) under `lights` (L,3) | (B,L,3): the pass of every `relight_*` /
+    `capture_rig` entry (the environment and rig-capture entries are held byte for byte to `relight_rig_device`).  Returns three values:
     `out`, the tuple `model.forward_lights` returned; `cm`, the compositing mask as a uint8 device tensor (`composite_mask_u8`, or
     `mask_u8` where that is None); `transfer`, True if `model` is a RelightNetLightingTransfer."""
     B, H, W, _ = x.shape
     transfer = _is_transfer(model)
-    K = camera_matrix((700.0 if transfer else 1570.0) if focal is None else focal, H, W)          # host: read without a sync
-    as_u8 = lambda m: (m if torch.is_tensor(m) else torch.as_tensor(np.asarray(m))).to(device=device, dtype=torch.uint8)
-    m_u8 = as_u8(mask_u8)
+    K = camera_matrix(_default_focal(transfer, focal), H, W)                                                     # host: read without a sync
+    m_u8 = _as_u8(mask_u8, device)
     mask = (m_u8.to(torch.float64).reshape(H, W, 1) / 255.0)                                                     # S1:580 / SLT:540
-    lights = (lights if torch.is_tensor(lights) else torch.as_tensor(np.asarray(lights, np.float32))).to(device=device, dtype=torch.float32)
-    lights = lights.reshape(-1, 3) if lights.dim() <= 2 else lights
+    lights = _as_lights(lights, device)
     out = model.forward_lights(x, epoch, K, mask, lights, float(ambient)) if transfer else model.forward_lights(x, epoch, K, mask, lights)
-    return out, (m_u8 if composite_mask_u8 is None else as_u8(composite_mask_u8)), transfer
+    return out, (m_u8 if composite_mask_u8 is None else _as_u8(composite_mask_u8, device)), transfer
 
 
 @torch.no_grad()
@@ -218,7 +214,6 @@ def relight_environment_device(model, images, mask_u8, env, n_lights: int = 64, 
                                fix_border: bool = False, composite_mask_u8=None, epoch: int = 200) -> torch.Tensor:
     """`relight_environment` up to the bytes ON THE DEVICE: (B,H,W,3) uint8 tensor, nothing copied back.  `images` / `mask_u8` /
     `env` / `rotation` may already be device tensors."""
-    from .lighting import _check_environment, environment_lights
     x = _as_batch(images).to(device)
     directions = _environment_directions(n_lights, min_z, x.device)
     env_d = _as_environment(env, x.device)
@@ -255,8 +250,6 @@ def relight_environment_frames(model, images, mask_u8, env, rotations, n_lights:
     `directions @ rotation`, so that the cell maps cannot differ from its in a last bit).  Per frame four launches -- the cell
     map, the integration, the rig combine, the image kernel -- and a fifth with `fix_border`; one more in total stacks the
     frames."""
-    from ._lib import GcfrError
-    from .lighting import _check_environment, _environment_lights
     x = _as_batch(images).to(device)
     directions = _environment_directions(n_lights, min_z, x.device)
     rots = torch.as_tensor(rotations, dtype=torch.float32).to(x.device)
@@ -280,8 +273,6 @@ def capture_rig(model, reference_images, mask_u8, lights, ridge: float = 1e-3, s
     compositing mask (`composite_mask_u8`, or `mask_u8` where that is None; u8 / 255).  A device tensor, not differentiable, no
     host synchronisation; it is what `relight_rig(_device)` and `RelightSession(light_rgb=...)` take.  `ridge` / `shared`: see
     `fit_light_rgb`, which also says why entries may be negative.  `model` / `ambient` / `focal` as in `relight_lights`."""
-    from ._lib import GcfrError
-    from .lighting import MAX_FIT_LIGHTS, fit_light_rgb
     x = _as_batch(reference_images).to(device)
     n = (lights.shape if torch.is_tensor(lights) else np.asarray(lights).shape)
     L = n[-2] if len(n) >= 2 else 1
@@ -371,13 +362,11 @@ class RelightSession:
                  miopen_find: bool = False, light_rgb=None):
         self.model, self.device, self.epoch, self.ambient, self.fix_border = model, torch.device(device), epoch, float(ambient), fix_border
         self.transfer = _is_transfer(model)
-        self.K = camera_matrix((700.0 if self.transfer else 1570.0) if focal is None else focal, H, W)       # host
-        as_u8 = lambda m: (m if torch.is_tensor(m) else torch.as_tensor(np.asarray(m))).to(device=self.device, dtype=torch.uint8)
-        self.m_u8 = as_u8(mask_u8).reshape(H, W)
-        self.cm = self.m_u8 if composite_mask_u8 is None else as_u8(composite_mask_u8).reshape(H, W)
+        self.K = camera_matrix(_default_focal(self.transfer, focal), H, W)                                   # host
+        self.m_u8 = _as_u8(mask_u8, self.device).reshape(H, W)
+        self.cm = self.m_u8 if composite_mask_u8 is None else _as_u8(composite_mask_u8, self.device).reshape(H, W)
         self.mask = (self.m_u8.to(torch.float64).reshape(H, W, 1) / 255.0)
-        lights = (lights if torch.is_tensor(lights) else torch.as_tensor(np.asarray(lights, np.float32))).to(device=self.device, dtype=torch.float32)
-        self.lights = (lights.reshape(-1, 3) if lights.dim() <= 2 else lights).contiguous()
+        self.lights = _as_lights(lights, self.device).contiguous()
         self.light_rgb = None if light_rgb is None else _as_light_rgb(light_rgb, self.device)     # a rig: one composite per face
         self.x = torch.zeros((B, H, W, 3), dtype=torch.float32, device=self.device)
         self.ambient_dev = torch.full((1,), self.ambient, dtype=torch.float32, device=self.device)   # (no host-to-device copy inside the capture)

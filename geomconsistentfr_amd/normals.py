@@ -26,10 +26,11 @@ class _NormalsFunction(torch.autograd.Function):
         B, _, H, W = depth.shape
         d = depth.detach().to(torch.float32).contiguous()
         out = torch.empty((B, 3, H, W), dtype=torch.float32, device=d.device)
+        from .block import _normals_fwd_args                     # (the one place that spells the entry's argument order)
         with torch.cuda.device(d.device):
-            _lib.check(_lib.load().gcfr_normals_fwd(d.data_ptr(), B, H, W, fx, fy, cx, cy, float(z_offset),
-                                                    int(negate_y), out.data_ptr(),
-                                                    torch.cuda.current_stream(d.device).cuda_stream), "gcfr_normals_fwd")
+            _lib.check(_lib.load().gcfr_normals_fwd(*_normals_fwd_args(
+                depth=d.data_ptr(), B=B, H=H, W=W, fx=fx, fy=fy, cx=cx, cy=cy, z_offset=float(z_offset), negate_y=int(negate_y),
+                normals=out.data_ptr(), stream=torch.cuda.current_stream(d.device).cuda_stream)), "gcfr_normals_fwd")
         ctx.save_for_backward(d)
         ctx.k = (fx, fy, cx, cy, float(z_offset), int(negate_y))
         return out

@@ -192,3 +192,50 @@ def test_a_stale_prepared_is_refused_not_rendered():
     r["rendered_images"].sum().backward()
     r2 = R.render_from_depth(d4.detach(), alb, l2.detach(), amb[:, 0], K, 1610.0, mask, prm)
     assert torch.equal(r["rendered_images"], r2["rendered_images"]) and float(d4.grad.abs().max()) > 0
+
+
+@pytest.mark.parametrize("L", [1, 16])
+def test_every_form_of_the_forward_issues_the_one_call_bits(L):
+    """One marshalling path (block._Forward) behind render_fwd, render_prepass and RenderFwdPlan: every form is the same
+    launches with the same arguments, so every output equals the one-call form's bit for bit -- at a shape whose last
+    16 x 4 tiles are ragged, with the normals stage fused (L = 1) and as its own launch (L = 16, and forced at L = 1).  The
+    one-call form's minimum distance is held to the C oracle on face 0, so that six identically wrong forms do not pass."""
+    import c_oracle
+    from geomconsistentfr_amd import RenderParams
+    from geomconsistentfr_amd import block as R
+    B, H, W = 2, 20, 36
+    depth, mask, light, amb, _, alb = _inputs(B=B, L=L, H=H, W=W)
+    prm = RenderParams(n_samples=24, dt=0.03)
+    cam = (1570.0, 1570.0, 18.0, 10.0, 1610.0)
+    args = (depth, mask, light, amb, None, alb)
+    assert R.normals_stage_for(L) == ("kernel" if L == 16 else "fused")
+    ref = R.render_fwd(*args, prm, want_argmin=True, camera=cam)                                          # (a)
+    ref = {k: v.clone() for k, v in ref.items() if v is not None}
+    assert set(ref) == {"unit_light_direction", "light_pt", "minimum_distance", "argmin", "shadow_mask_weights", "full_shading",
+                        "final_shading", "rendered_images", "surface_normals"}
+    plan = lambda **kw: R.RenderFwdPlan(B, L, H, W, prm, DEV, want_argmin=True, camera=cam, **kw)
+
+    def same(name, out):
+        torch.cuda.synchronize()
+        for k, v in ref.items():
+            assert torch.equal(out[k], v), (name, k)
+
+    pre = R.render_prepass(depth, mask, light, prm, want_argmin=True)
+    same("prepass, then march", R.render_fwd(*args, prm, want_argmin=True, camera=cam, prepared=pre))    # (b)
+    p = plan()
+    same("plan, eager", p(*args))                                                                         # (c)
+    same("plan, one graph", p.capture(*args).replay())                                                    # (d)
+    two = plan().capture_split(*args)                                                                     # (e)
+    for v in list(two.out.values()) + [two.ws]:
+        if v is not None:
+            v.zero_()
+    two.replay_prepass()
+    same("plan, two graphs", two.replay_march())
+    if L == 1:
+        k = plan(normals_stage="kernel")                                                                  # (f)
+        assert k.normals_stage == "kernel"
+        same("plan, normals stage as its own launch", k(*args))
+    _, pt_o = c_oracle.light_prep(light[0].cpu().numpy(), clamp_z_min=0.0)
+    md_o, _ = c_oracle.shadow_min_distance(depth[:1].cpu().numpy(), mask[:1].cpu().numpy(), pt_o.reshape(1, L, 3),
+                                           c_oracle.sample_table(prm.t0, prm.dt, prm.n_samples))
+    assert np.array_equal(ref["minimum_distance"][:1].cpu().numpy(), md_o)
