@@ -160,6 +160,144 @@ __global__ __launch_bounds__(256) void shadow_fwd_kernel(ShadowArgs a)
     }
 }
 
+// ---- stride 8 (the stride every benchmark shape selects): four tiles side by side in a wave -------------------------------
+// A tile of 16 x 16 extended cells is one DPP row of 16 lanes and a lane owns a 4 x 4 patch of it: lane = 4 * quadrant + 2 * py + px
+// with the patch at rows 8 qy + 4 py, columns 8 qx + 4 px of the tile -- an 8 x 8 quadrant is one DPP quad, so the quadrant sums
+// are two quad_perm steps, the slopes and their four IEEE divisions are evaluated once for four tiles (per-row values in VGPRs),
+// and the residual extrema are 16-lane row reductions; lane 15 of a row stores its tile's record.
+//
+// Summation order: a 4 x 4 patch is four 2 x 2 patches, each summed (v00 + v01) + (v10 + v11) and then combined as the balanced
+// tree over the quadrant's sixteen 2 x 2 patches in row-major order that one wave per tile formed with row_sum_f32 (pairs along
+// the row, the row, two rows, four); the residuals keep the per-2x2 arithmetic (base, base + pa, base - pb).  So the record of a
+// tile of proper cells only is what it always was, bit for bit.  Tiles that touch the wrap row / column or the plane's end take the
+// same layout with wrap and validity decided per cell (kEdge): their sums used to be formed in another order, and their records
+// may differ from that in the last bits -- any (a, b) is valid, the residual extrema make it so.
+template <int CTRL>
+__device__ inline float dpp_f32(float v)  // (controls under which every lane reads a lane of its row: quad_perm, row_ror, mirrors)
+{
+    return __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), CTRL, 0xf, 0xf, false));
+}
+__device__ inline float quad_sum_f32(float h0, float h1)  // h0, h1: the lane's halves of two rows of 2 x 2 patches
+{
+    const float r0 = h0 + dpp_f32<0xb1>(h0), r1 = h1 + dpp_f32<0xb1>(h1);  // quad_perm [1,0,3,2]: the row of four patches
+    const float t = r0 + r1;                                              // two rows
+    return t + dpp_f32<0x4e>(t);                                          // quad_perm [2,3,0,1]: the quadrant, in all four lanes
+}
+__device__ inline bool f32_finite(float v) { return __builtin_amdgcn_class(v, 0x1f8); }  // (+-normal, +-subnormal, +-0)
+
+// tiles of proper cells only ("inner": rows [1, zb_inner(H)], columns [1, zb_inner(W)] of the stride-8 grid): (8 t + 15 <= extent)
+__host__ __device__ inline int zb_inner(int extent) { return extent < 15 ? 0 : (extent - 15) >> 3; }
+
+template <bool kEdge>
+__device__ inline void build_zbounds_four(int ti, int tj, bool live, int b, const float *__restrict__ depth,
+                                          float4 *__restrict__ zb, int H, int W)
+{
+    const int sub = threadIdx.x & 15;
+    const int qy = sub >> 3, qx = (sub >> 2) & 1, py = (sub >> 1) & 1, px = sub & 1;
+    const int er0 = (ti << 3) + (qy << 3) + (py << 2), ec0 = (tj << 3) + (qx << 3) + (px << 2);
+    const float *z = depth + (size_t)b * H * W;
+    float v[4][4];
+    bool fin[4][4];
+    if (!kEdge) {
+        const float *p = z + (size_t)(er0 - 1) * W + (ec0 - 1);
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                v[i][j] = p[(size_t)i * W + j];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                fin[i][j] = f32_finite(v[i][j]);
+    } else {
+        // extended row 0 / column 0 is the wrap partner (a cell of the bands, not of the means); rows past H and columns past W
+        // are no cells: loaded from row / column 0 (inside the plane) and replaced by NaN, which every use below drops
+        const float *rowp[4];
+        int col[4];
+        bool rin[4], cin[4], rprop[4], cprop[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int er = er0 + i, ec = ec0 + i;
+            rin[i] = er <= H;
+            cin[i] = ec <= W;
+            rprop[i] = er >= 1;
+            cprop[i] = ec >= 1;
+            rowp[i] = z + (size_t)(rin[i] ? (er == 0 ? H - 1 : er - 1) : 0) * W;
+            col[i] = cin[i] ? (ec == 0 ? W - 1 : ec - 1) : 0;
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                v[i][j] = rowp[i][col[j]];
+#pragma unroll
+        for (int i = 0; i < 4; ++i)
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                v[i][j] = (rin[i] && cin[j]) ? v[i][j] : __builtin_nanf("");
+                fin[i][j] = f32_finite(v[i][j]) && rprop[i] && cprop[j];
+            }
+    }
+    // slopes from the means of the finite proper cells of the four quadrants
+    float hc[2], hs[2];
+#pragma unroll
+    for (int sy = 0; sy < 2; ++sy) {
+        float pc[2], ps[2];
+#pragma unroll
+        for (int sx = 0; sx < 2; ++sx) {
+            const int i = 2 * sy, j = 2 * sx;
+            pc[sx] = ((fin[i][j] ? 1.0f : 0.0f) + (fin[i][j + 1] ? 1.0f : 0.0f)) + ((fin[i + 1][j] ? 1.0f : 0.0f) + (fin[i + 1][j + 1] ? 1.0f : 0.0f));
+            ps[sx] = ((fin[i][j] ? v[i][j] : 0.0f) + (fin[i][j + 1] ? v[i][j + 1] : 0.0f)) +
+                     ((fin[i + 1][j] ? v[i + 1][j] : 0.0f) + (fin[i + 1][j + 1] ? v[i + 1][j + 1] : 0.0f));
+        }
+        hc[sy] = pc[0] + pc[1];
+        hs[sy] = ps[0] + ps[1];
+    }
+    const float cnt = quad_sum_f32(hc[0], hc[1]), sz = quad_sum_f32(hs[0], hs[1]);
+    const float m = sz / cnt;  // this lane's quadrant (NaN where it is empty)
+    float nmin = fminf(cnt, dpp_f32<0x128>(cnt));  // row_ror:8, row_ror:4: the smallest count of the four quadrants
+    nmin = fminf(nmin, dpp_f32<0x124>(nmin));
+    // columns: u = m00 + m10 in the lanes of the left quadrants, m01 + m11 in the right ones; rows: w = m00 + m01 in the upper
+    // quadrants, m10 + m11 in the lower ones; the rotations fetch the other pair
+    const float u = m + dpp_f32<0x128>(m), uo = dpp_f32<0x124>(u);
+    const float w = m + dpp_f32<0x141>(m), wo = dpp_f32<0x128>(w);  // row_half_mirror: quadrant q <-> q ^ 1
+    const float ca = ((qx ? u : uo) - (qx ? uo : u)) * 0.0625f, cb = ((qy ? w : wo) - (qy ? wo : w)) * 0.0625f;
+    float pa = 0.0f, pb = 0.0f;
+    if (nmin > 0.0f) {  // all four quadrants populated
+        if (ca - ca == 0.0f)
+            pa = fminf(fmaxf(ca, -4.0f), 4.0f);   // dz/dX: X grows with the column
+        if (cb - cb == 0.0f)
+            pb = -fminf(fmaxf(cb, -4.0f), 4.0f);  // dz/dY: Y falls with the row
+    }
+    // residual extrema over every cell (fminf / fmaxf drop NaN cells)
+    float lo = __builtin_inff(), hi = -__builtin_inff();
+#pragma unroll
+    for (int sy = 0; sy < 2; ++sy)
+#pragma unroll
+        for (int sx = 0; sx < 2; ++sx) {
+            const int i = 2 * sy, j = 2 * sx;
+            const float X0 = (float)(ec0 + j - 1) - 0.5f * (float)W, Y0 = 0.5f * (float)H - (float)(er0 + i - 1);
+            const float base = __builtin_fmaf(pa, X0, pb * Y0);  // the plane at the 2 x 2 patch's first cell; +pa per column, -pb per row
+            const float r00 = v[i][j] - base, r01 = v[i][j + 1] - (base + pa), r10 = v[i + 1][j] - (base - pb),
+                        r11 = v[i + 1][j + 1] - ((base + pa) - pb);
+            lo = fminf(lo, fminf(fminf(r00, r01), fminf(r10, r11)));
+            hi = fmaxf(hi, fmaxf(fmaxf(r00, r01), fmaxf(r10, r11)));
+        }
+    int slo = f32_sortable(lo), shi = f32_sortable(-hi);
+    slo = dpp_min_step<0x111, 0xf>(slo);  // row_shr:1, 2, 4, 8 -> lane 15 of each row holds the row's minimum
+    shi = dpp_min_step<0x111, 0xf>(shi);
+    slo = dpp_min_step<0x112, 0xf>(slo);
+    shi = dpp_min_step<0x112, 0xf>(shi);
+    slo = dpp_min_step<0x114, 0xf>(slo);
+    shi = dpp_min_step<0x114, 0xf>(shi);
+    slo = dpp_min_step<0x118, 0xf>(slo);
+    shi = dpp_min_step<0x118, 0xf>(shi);
+    if (sub == 15 && live)
+        zb[(size_t)b * zb_slot(H, W) + (size_t)ti * ((W >> 3) + 1) + tj] = make_float4(pa, pb, f32_unsortable(slo), -f32_unsortable(shi));
+}
+
+// ---- strides 16 and 32: one wave per tile ------------------------------------------------------------------------------------
 __device__ inline void build_zbounds_tile(int tile, int ls, int b, const float *__restrict__ depth,
                                           float4 *__restrict__ zb, int H, int W)
 {
@@ -170,40 +308,6 @@ __device__ inline void build_zbounds_tile(int tile, int ls, int b, const float *
     const int ti = tile / ntw, tj = tile - ti * ntw;
     const int side = 2 << ls;
     const float *z = depth + (size_t)b * H * W;
-    if (ls == 3 && ti >= 1 && tj >= 1 && (ti << 3) + 15 <= H && (tj << 3) + 15 <= W) {
-        // Fast path (the common stride, a tile of proper cells only): each lane owns one 2x2 patch of its row's
-        // quadrant, loads it once and uses it for both passes; no bounds tests, no reloads.
-        const int q = lane >> 4, iy = (lane >> 2) & 3, ix = lane & 3;
-        const int er = (ti << 3) + ((q >> 1) << 3) + (iy << 1), ec = (tj << 3) + ((q & 1) << 3) + (ix << 1);
-        const float *p = z + (size_t)(er - 1) * W + (ec - 1);
-        const float v00 = p[0], v01 = p[1], v10 = p[W], v11 = p[W + 1];
-        const bool f00 = v00 - v00 == 0.0f, f01 = v01 - v01 == 0.0f, f10 = v10 - v10 == 0.0f, f11 = v11 - v11 == 0.0f;
-        float cnt = ((f00 ? 1.0f : 0.0f) + (f01 ? 1.0f : 0.0f)) + ((f10 ? 1.0f : 0.0f) + (f11 ? 1.0f : 0.0f));
-        float sz = ((f00 ? v00 : 0.0f) + (f01 ? v01 : 0.0f)) + ((f10 ? v10 : 0.0f) + (f11 ? v11 : 0.0f));
-        cnt = row_sum_f32(cnt);
-        sz = row_sum_f32(sz);
-        const float n00 = lane_value(cnt, 15), n01 = lane_value(cnt, 31), n10 = lane_value(cnt, 47), n11 = lane_value(cnt, 63);
-        float pa = 0.0f, pb = 0.0f;
-        if (n00 > 0.0f && n01 > 0.0f && n10 > 0.0f && n11 > 0.0f) {
-            const float m00 = lane_value(sz, 15) / n00, m01 = lane_value(sz, 31) / n01;
-            const float m10 = lane_value(sz, 47) / n10, m11 = lane_value(sz, 63) / n11;
-            const float ca = ((m01 + m11) - (m00 + m10)) * 0.0625f, cb = ((m10 + m11) - (m00 + m01)) * 0.0625f;
-            if (ca - ca == 0.0f)
-                pa = fminf(fmaxf(ca, -4.0f), 4.0f);
-            if (cb - cb == 0.0f)
-                pb = -fminf(fmaxf(cb, -4.0f), 4.0f);
-        }
-        const float X0 = (float)(ec - 1) - 0.5f * (float)W, Y0 = 0.5f * (float)H - (float)(er - 1);
-        const float base = __builtin_fmaf(pa, X0, pb * Y0);  // the plane at the patch's first cell; +pa per column, -pb per row
-        const float r00 = v00 - base, r01 = v01 - (base + pa), r10 = v10 - (base - pb), r11 = v11 - ((base + pa) - pb);
-        const float lo = fminf(fminf(r00, r01), fminf(r10, r11));  // (fminf / fmaxf drop NaN cells)
-        const float hi = fmaxf(fmaxf(r00, r01), fmaxf(r10, r11));
-        const float wlo = f32_unsortable(wave_min_i32(f32_sortable(lo)));
-        const float whi = -f32_unsortable(wave_min_i32(f32_sortable(-hi)));
-        if (lane == 0)
-            zb[(size_t)b * zb_slot(H, W) + tile] = make_float4(pa, pb, wlo, whi);
-        return;
-    }
     // pass 1: slopes from the means of the tile's four s x s quadrants (finite proper cells only).  Row q of
     // the wave (16 lanes) owns quadrant q = 2*qy + qx and strides over its cells, so the four sums come out of
     // DPP row reductions with no cross-row traffic.
@@ -253,13 +357,27 @@ __device__ inline void build_zbounds_tile(int tile, int ls, int b, const float *
         zb[(size_t)b * zb_slot(H, W) + tile] = make_float4(pa, pb, wlo, whi);
 }
 
-// kZbTilesPerWave tiles per wave, one after the other: a block per four tiles was 273 blocks per 256 x 256 image, half of the
-// prepass' workgroups -- and the prepass runs at the pace they are dispatched (see the repack job)
-#ifndef GCFR_ZB_TILES_PER_WAVE
-#define GCFR_ZB_TILES_PER_WAVE 2
+// The bounds job's share of the grid.  At stride 8 a wave takes kZbStepsPerWave consecutive STEPS of four tiles, so that the
+// stride's derivation (zb_log2_stride: an f64 division) and the tile coordinates' division are paid once for that many: the
+// steps run through the inner tiles first (row-major over [1, nih] x [1, niw]; after the first step the coordinates advance
+// by four columns), then through the others -- the rows 0 and nih+1 ... of the grid whole, then columns 0 and niw+1 ... of the
+// inner rows.  Fewer, longer workgroups: the prepass runs at the pace its workgroups are dispatched (see the repack job).
+// Measured on MI355X, 256 x 256 (profiles/prepass_diet_ab.txt): four steps per wave (18 workgroups per image) 35.4 us per
+// benchmark step with four batches in flight, two 35.8, and the same within 1 % one batch at a time.
+#ifndef GCFR_ZB_STEPS_PER_WAVE
+#define GCFR_ZB_STEPS_PER_WAVE 4
 #endif
-constexpr int kZbTilesPerWave = GCFR_ZB_TILES_PER_WAVE;
-__device__ inline void build_zbounds_block(int block, int b, const float *__restrict__ depth,
+constexpr int kZbStepsPerWave = GCFR_ZB_STEPS_PER_WAVE;
+__host__ __device__ inline int zb_inner_steps(int H, int W) { return (zb_inner(H) * zb_inner(W) + 3) >> 2; }
+__host__ __device__ inline int zb_steps(int H, int W)
+{
+    const int n = ((H >> 3) + 1) * ((W >> 3) + 1);
+    return zb_inner_steps(H, W) + ((n - zb_inner(H) * zb_inner(W) + 3) >> 2);
+}
+// workgroups of the job: sized for stride 8; a coarser stride has fewer tiles than these have waves, and strides over them anyway
+__host__ __device__ inline int zb_job_blocks(int H, int W) { return (zb_steps(H, W) + 4 * kZbStepsPerWave - 1) / (4 * kZbStepsPerWave); }
+
+__device__ inline void build_zbounds_block(int block, int n_blocks, int b, const float *__restrict__ depth,
                                            float4 *__restrict__ zb, int H, int W, int N,
                                            const double *__restrict__ t_table, int group)
 {
@@ -268,8 +386,44 @@ __device__ inline void build_zbounds_block(int block, int b, const float *__rest
         zb[(size_t)b * zb_slot(H, W) + zb_max_tiles(H, W) - 1] =
             make_float4(0.0f, 0.0f, -__builtin_inff(), __builtin_inff());
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    for (int t = 0; t < kZbTilesPerWave; ++t)
-        build_zbounds_tile((block * kZbTilesPerWave + t) * 4 + wave, ls, b, depth, zb, H, W);
+    if (ls != 3) {
+        const int n = ((H >> ls) + 1) * ((W >> ls) + 1);
+        for (int tile = block * 4 + wave; tile < n; tile += n_blocks * 4)
+            build_zbounds_tile(tile, ls, b, depth, zb, H, W);
+        return;
+    }
+    const int row = (threadIdx.x >> 4) & 3;  // the wave's DPP row = which of the step's four tiles
+    const int ntw = (W >> 3) + 1, nth = (H >> 3) + 1;
+    const int nih = zb_inner(H), niw = zb_inner(W);
+    const int n_edge = nth * ntw - nih * niw, in_steps = zb_inner_steps(H, W), steps = zb_steps(H, W);
+    const int step0 = (block * 4 + wave) * kZbStepsPerWave;
+    int ti = 0, tj = 0;  // position in the inner list
+    if (step0 < in_steps) {
+        const int idx = step0 * 4 + row;
+        ti = idx / niw;
+        tj = idx - ti * niw;
+    }
+#pragma unroll 1
+    for (int s = 0; s < kZbStepsPerWave; ++s) {
+        const int step = step0 + s;
+        if (step < in_steps) {
+            build_zbounds_four<false>(1 + min(ti, nih - 1), 1 + tj, ti < nih, b, depth, zb, H, W);  // (past the list: a tile to load from, no store)
+            tj += 4;
+            while (tj >= niw) {
+                tj -= niw;
+                ++ti;
+            }
+        } else if (step < steps) {
+            const int k = min((step - in_steps) * 4 + row, n_edge - 1);
+            const int n_full = (nth - nih) * ntw;  // whole rows: row 0 and the rows behind the inner ones
+            const bool side = k >= n_full;
+            const int num = side ? k - n_full : k, den = side ? ntw - niw : ntw;
+            const int quo = num / den, rem = num - quo * den;
+            const int eti = side ? 1 + quo : (quo == 0 ? 0 : nih + quo);
+            const int etj = side ? (rem == 0 ? 0 : niw + rem) : rem;
+            build_zbounds_four<true>(eti, etj, (step - in_steps) * 4 + row < n_edge, b, depth, zb, H, W);
+        }
+    }
 }
 
 // diag[4]: {min (c + r), -max (c + r), min (c - r), -max (c - r)} over the non-zero cells: the mask's diagonal extents (the
@@ -624,7 +778,7 @@ __global__ __launch_bounds__(256) void build_quad_kernel(const float *__restrict
     const int bx = (int)blockIdx.x - hz_blocks;
     if (bx < zb_blocks) {
         if (GCFR_JOB(1))
-            build_zbounds_block(bx, b, depth, zb, H, W, N, t_table, group);
+            build_zbounds_block(bx, zb_blocks, b, depth, zb, H, W, N, t_table, group);
         return;
     }
     if (bx < zb_blocks + stat_blocks) {
@@ -944,7 +1098,7 @@ static int shadow_fwd_impl(const float *depth, const uint8_t *mask_u8, int32_t m
         const bool lds_stage = !own && !ksplit && lds_fits && (kn.lds_stage < 0 ? (GCFR_LDS_STAGE_AUTO != 0) : (kn.lds_stage == 1));
         const Schedule sch = own ? kGridOwn : (ksplit ? kKSplit : (lds_stage ? kGridLds : kGrid));
         const int quad_blocks = (texels + 256 * GCFR_QUAD_PER_THREAD - 1) / (256 * GCFR_QUAD_PER_THREAD);
-        const int zb_blocks = use_zb ? (zb_max_tiles(H, W) + 4 * kZbTilesPerWave - 1) / (4 * kZbTilesPerWave) : 0;  // sized for the finest stride
+        const int zb_blocks = use_zb ? zb_job_blocks(H, W) : 0;  // sized for the finest stride
         const int bitmap_blocks = lds_stage ? ((H * W) / 32 + 255) / 256 : 0;
         // horizon tables: for the trailing loop of the grid schedule's bounds-skipping march (not the k-split's quarter
         // ranges, not the LDS-staged variant), where the shape and the planes' alignment allow vector loads

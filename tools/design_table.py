@@ -54,6 +54,27 @@ def small_kernels(tag):
     return out
 
 
+def prepass_row(tag, name, what, sk):
+    """the prepass' row from the counters the fwd leg's PMC passes collected for it (profiles/<tag>_fwd_pmc.json), or None.
+    60 VGPRs, eight waves per SIMD (tests/test_kernel_resources.py: no scratch); algorithmic bytes per launch of 8 faces: depth 4 +
+    mask 1 read, texels 16 B x 257^2 / 256^2 written -> ~21.1 B / pixel."""
+    p = os.path.join(ROOT, "profiles", "%s_fwd_pmc.json" % tag)
+    if not os.path.exists(p) or name not in sk:
+        return None
+    c = next((v for k, v in json.load(open(p)).items() if name in k), None)
+    if not c or "SQ_INSTS_VALU" not in c:
+        return None
+    by = {k: c.get("SQ_INSTS_VALU_" + k, 0.0) for k in SPEC if k != "OTHER"}
+    by["OTHER"] = max(c["SQ_INSTS_VALU"] - sum(by.values()), 0.0)
+    us = sk[name][0]
+    frac = sum(by[k] * SPEC[k] for k in by) / (CAP * us * 1e-6)
+    hbm = (2.0 * c.get("FETCH_SIZE", 0.0) + c.get("WRITE_SIZE", 0.0)) * 1024.0
+    algo = 8 * (PIX * 5.0 + 257 * 257 * 16.0)
+    return "| `%s` | %s | %.1f us (%s profile, %d calls) | 60 / 8 | %.2f M (+ %.2f M scalar, %d waves) | %.2f (launch-sized: ~10 us of it is the launch floor) | %.0f %% | %.1f / %.1f MB = %.2f |" % (
+        name, what, us, sk[name][2], sk[name][1], c["SQ_INSTS_VALU"] / 1e6, c.get("SQ_INSTS_SALU", 0.0) / 1e6, c.get("SQ_WAVES", 0),
+        frac, 100.0 * c["SQ_WAIT_ANY"] / c["SQ_WAVE_CYCLES"], hbm / 1e6, algo / 1e6, hbm / algo)
+
+
 def main():
     args = sys.argv[1:]
     tag = args[args.index("--tag") + 1] if "--tag" in args else "r05"
@@ -74,7 +95,10 @@ def main():
     sk = small_kernels(tag)
     for name, what in (("build_quad_kernel", "prepass: repack, statistics, bounds tiles, horizon tables, light prep T8:357-363 (`gcfr_shadow.hip`); own enqueue since ABI 5 (`gcfr_options.phase`)"),
                        ("light_prep_bwd_kernel", "autograd of T8:357-363")):
-        if name in sk:
+        pre = prepass_row(tag, name, what, sk) if name == "build_quad_kernel" else None
+        if pre:
+            rows.append(pre)
+        elif name in sk:
             rows.append("| `%s` | %s | %.1f us (%s profile, %d calls) | -- | -- | -- (latency) | -- | ~1.0 |" % (name, what, sk[name][0], sk[name][2], sk[name][1]))
     table = "\n".join(rows)
     note = ("\n\n(generated by `tools/design_table.py --tag %s --write` from `profiles/pmc_summary.json`, library hash `%s`, and "

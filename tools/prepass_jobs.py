@@ -5,6 +5,14 @@
     tools/prepass_jobs.py run [--faces 8]  (GPU)  per library: the prepass alone (gcfr_options.phase = 1) as a hipGraph, replayed one at a
                                                   time on one stream; fenced wall time per replay and the HIP-event time of 200 single
                                                   replays -> gpurun_out/prepass_jobs.json
+                          [--prefix P]            the libraries lib/<P><mask>.so instead of lib/prepass_jobs_<mask>.so (another build of
+                                                  the same masks, e.g. the parent commit's)
+                          [--out FILE]            the JSON goes to FILE instead (so that two builds' results can lie side by side)
+                          [--timeout S]           time limit of each library's child process (default 120 s)
+
+`run` starts one child process per library, each under its own time limit, and STOPS at the first child that fails (a non-zero
+status, a time-out or no result line): what has faulted the device once is not given the next library to fault it again.  Its exit
+status is then 1 and the JSON names the failure.
 
 build_quad_kernel's grid is [horizon tables | depth-bounds tiles | statistics chunks | (bitmap) | repack]; -DGCFR_PREPASS_JOBS leaves the
 grid as it is and makes the blocks of the jobs whose bit is clear return at once (1 horizon, 2 bounds, 4 statistics, 8 bitmap, 16 repack),
@@ -81,22 +89,37 @@ def one(faces):
                       "event_us_median": 1e3 * ev_ms[len(ev_ms) // 2], "event_us_min": 1e3 * ev_ms[0]}))
 
 
-def run(faces):
+def run(faces, prefix=None, limit=120.0, out_file=None):
     out = {"faces": faces, "how": __doc__.split("\n\n")[1], "libraries": {}}
+    failed = None
     for name, m in MASKS:
-        lib = lib_of(m)
+        lib = lib_of(m) if prefix is None else os.path.join(LIB_DIR, "%s%d.so" % (prefix, m))
         if not os.path.exists(lib):
             continue
-        r = subprocess.run([sys.executable, os.path.abspath(__file__), "one", str(faces)], env=dict(os.environ, GCFR_HIP_LIB=lib),
-                           capture_output=True, text=True)
         try:
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "one", str(faces)], env=dict(os.environ, GCFR_HIP_LIB=lib),
+                               capture_output=True, text=True, timeout=limit)
+            if r.returncode != 0:
+                raise RuntimeError("exit status %d: %s" % (r.returncode, (r.stderr or r.stdout)[-600:]))
             out["libraries"][name] = dict(json.loads(r.stdout.strip().splitlines()[-1]), mask=m)
-        except Exception:
-            out["libraries"][name] = {"mask": m, "error": (r.stderr or r.stdout)[-600:]}
+        except subprocess.TimeoutExpired:
+            failed = out["libraries"][name] = {"mask": m, "error": "no result within %.0f s" % limit}
+        except Exception as e:
+            failed = out["libraries"][name] = {"mask": m, "error": str(e)[-700:]}
         print(name, out["libraries"][name], flush=True)
+        if failed:
+            out["stopped_at"] = name   # the libraries behind it were not run
+            break
     os.makedirs(os.path.join(REPO, "gpurun_out"), exist_ok=True)
     with open(os.path.join(REPO, "gpurun_out", "prepass_jobs.json"), "w") as f:
         json.dump(out, f, indent=1)
+    if out_file:
+        os.replace(f.name, out_file)
+    return 1 if failed else 0
+
+
+def _arg(flag, default, kind):
+    return kind(sys.argv[sys.argv.index(flag) + 1]) if flag in sys.argv else default
 
 
 if __name__ == "__main__":
@@ -106,6 +129,6 @@ if __name__ == "__main__":
     elif what == "one":
         one(int(sys.argv[2]))
     elif what == "run":
-        run(int(sys.argv[sys.argv.index("--faces") + 1]) if "--faces" in sys.argv else 8)
+        sys.exit(run(_arg("--faces", 8, int), _arg("--prefix", None, str), _arg("--timeout", 120.0, float), _arg("--out", None, str)))
     else:
         sys.exit(__doc__)
