@@ -116,6 +116,7 @@ _SIGNATURES = {
     "gcfr_light_fit_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i, _i]),
     "gcfr_light_fit_normal": (_i, [_p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "gcfr_light_fit_solve": (_i, [_p, _p, _i, _i, _d, _i, _p, _p, _p]),
+    "gcfr_light_fit_solve_nonneg": (_i, [_p, _p, _i, _i, _d, _i, _i, _p, _p, _p, _p]),
     "gcfr_copy_probe": (_i, [_p, _p, ctypes.c_size_t, _p]),
 }
 

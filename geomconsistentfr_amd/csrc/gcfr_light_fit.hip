@@ -3,7 +3,7 @@
 //
 //     image[b,c,p] ~ albedo[b,c,p] sum_l x[b,l,c] final[b,l,p]        G_c[l,l'] = sum_p w a_c^2 f_l f_l'      r_c[l] = sum_p w a_c I_c f_l
 //
-// Three kernels, no floating-point atomic, no cross-lane reduction, every sum in f64 in a FIXED order (include/gcfr.h):
+// Three kernels per fit, no floating-point atomic, no cross-lane reduction, every sum in f64 in a FIXED order (include/gcfr.h):
 //
 //   partials   a workgroup of 256 lanes owns one face and walks that face's chunks of kFitChunk pixels j, j + groups, ... ascending.
 //              Per chunk it stages in LDS the L rows of `final` (f32, row stride kFitStride floats) and, per channel, q = (w a) a and
@@ -18,6 +18,8 @@
 //   solve      one workgroup of 64 lanes (one wave) per (rig, channel): the faces' systems added in ascending b (one shared rig),
 //              the ridge, a left-looking Cholesky factorisation in LDS with lane i owning row i, forward and back substitution; one
 //              rounding to f32.
+//   non-negative solve   the same system under x >= 0 by an active-set method: the same factorisation restricted to the lights of
+//              the passive set, once per step, in place of `solve`.
 //
 // Work per pixel and channel at L lights, N = L (L + 3) / 2 entries: 3 N f64 operations (two products, one sum) + 2 N conversions
 // f32 -> f64, 3 N LDS reads (8 + 4 + 4 bytes); from memory 4 L + 28 bytes per pixel (final, albedo, image, weight), once.
@@ -162,18 +164,15 @@ __global__ __launch_bounds__(kFitLanes) void light_fit_finish_kernel(const doubl
     }
 }
 
-// Lane i owns row i.  A holds the system's lower triangle, then the factor's strictly lower triangle; `diag` the factor's diagonal.
-__global__ __launch_bounds__(kSolveLanes) void light_fit_solve_kernel(const double *__restrict__ gram, const double *__restrict__ rhs,
-                                                                      uint32_t B, uint32_t L, double ridge, uint32_t rgb_batch,
-                                                                      float *__restrict__ rgb, int32_t *__restrict__ info)
+constexpr uint32_t kSolveStride = (uint32_t)kFitMaxLights + 1u;   // row stride in doubles: lanes reading one column hit 32 banks
+
+// Both solves start here.  Lane i < L: the lower triangle of row i of the summed system (faces in ascending b) into A, the relative
+// ridge on its diagonal; -> the summed right-hand side r_i (0 for a lane without a row).  Ends behind a barrier.
+__device__ __forceinline__ double fit_load_system(const double *__restrict__ gram, const double *__restrict__ rhs, uint32_t B, uint32_t L,
+                                                  double ridge, uint32_t rgb_batch, uint32_t c, uint32_t rig, double *A, double *shift)
 {
-    constexpr uint32_t S = (uint32_t)kFitMaxLights + 1u;             // row stride in doubles: lanes reading one column hit 32 banks
-    __shared__ double A[kFitMaxLights * (kFitMaxLights + 1)];
-    __shared__ double diag[kFitMaxLights];
-    __shared__ double piv[kFitMaxLights];
-    __shared__ double sol[kFitMaxLights];
-    __shared__ double shift;
-    const uint32_t i = threadIdx.x, c = blockIdx.x, rig = blockIdx.y;
+    constexpr uint32_t S = kSolveStride;
+    const uint32_t i = threadIdx.x;
     const uint32_t faces = rgb_batch == 1u ? B : 1u, first = rgb_batch == 1u ? 0u : rig;
     const bool row = i < L;
     double y = 0.0;
@@ -193,12 +192,29 @@ __global__ __launch_bounds__(kSolveLanes) void light_fit_solve_kernel(const doub
         double trace = 0.0;
         for (uint32_t l = 0; l < L; ++l)
             trace = trace + A[l * S + l];
-        shift = ridge * (trace / (double)L);
+        *shift = ridge * (trace / (double)L);
     }
     __syncthreads();
     if (row)
-        A[i * S + i] = A[i * S + i] + shift;
+        A[i * S + i] = A[i * S + i] + *shift;
     __syncthreads();
+    return y;
+}
+
+// Lane i owns row i.  A holds the system's lower triangle, then the factor's strictly lower triangle; `diag` the factor's diagonal.
+__global__ __launch_bounds__(kSolveLanes) void light_fit_solve_kernel(const double *__restrict__ gram, const double *__restrict__ rhs,
+                                                                      uint32_t B, uint32_t L, double ridge, uint32_t rgb_batch,
+                                                                      float *__restrict__ rgb, int32_t *__restrict__ info)
+{
+    constexpr uint32_t S = kSolveStride;
+    __shared__ double A[kFitMaxLights * (kFitMaxLights + 1)];
+    __shared__ double diag[kFitMaxLights];
+    __shared__ double piv[kFitMaxLights];
+    __shared__ double sol[kFitMaxLights];
+    __shared__ double shift;
+    const uint32_t i = threadIdx.x, c = blockIdx.x, rig = blockIdx.y;
+    const bool row = i < L;
+    double y = fit_load_system(gram, rhs, B, L, ridge, rgb_batch, c, rig, A, &shift);
 
     int32_t bad = 0;
     for (uint32_t k = 0; k < L; ++k) {                               // (uniform)
@@ -252,6 +268,179 @@ __global__ __launch_bounds__(kSolveLanes) void light_fit_solve_kernel(const doub
         out[(size_t)i * 3u] = (float)sol[i];
     if (i == 0u)
         info[rig * 3u + c] = 0;
+}
+
+// The non-negative solve (include/gcfr.h states the order): Lawson and Hanson's active-set method on the normal equations.  Lane i
+// owns light i -- its r_i, x_i, s_i, w_i are registers; the passive set P is a wave-uniform 64-bit mask and every loop over it a
+// scalar loop over its set bits.  A's lower triangle (the system) stays intact: A[i,j] for j > i is read as A[j,i].  The factor's
+// strictly lower triangle lives TRANSPOSED in A's unused upper triangle, C[i,m] at A[m * S + i] for i > m (lanes reading one column
+// of C read consecutive doubles), its diagonal in `diag`.
+__global__ __launch_bounds__(kSolveLanes) void light_fit_solve_nonneg_kernel(const double *__restrict__ gram,
+                                                                             const double *__restrict__ rhs, uint32_t B, uint32_t L,
+                                                                             double ridge, uint32_t rgb_batch, uint32_t cap,
+                                                                             float *__restrict__ rgb, int32_t *__restrict__ info,
+                                                                             int32_t *__restrict__ solves)
+{
+    constexpr uint32_t S = kSolveStride;
+    __shared__ double A[kFitMaxLights * (kFitMaxLights + 1)];
+    __shared__ double diag[kFitMaxLights];
+    __shared__ double sol[kFitMaxLights];
+    __shared__ double xs[kFitMaxLights];                             // x, for the other lanes' w
+    __shared__ double lane_val[kFitMaxLights];                       // r, then w or the step quotients: what arg-max / arg-min read
+    __shared__ double piv;
+    __shared__ double shift;
+    const uint32_t i = threadIdx.x, c = blockIdx.x, rig = blockIdx.y;
+    const bool row = i < L;
+    const double r = fit_load_system(gram, rhs, B, L, ridge, rgb_batch, c, rig, A, &shift);
+    lane_val[i] = r;
+    xs[i] = 0.0;
+    __syncthreads();
+    double largest = 0.0;
+    for (uint32_t l = 0; l < L; ++l) {                               // (uniform; a NaN never enters)
+        const double v = fabs(lane_val[l]);
+        largest = v > largest ? v : largest;
+    }
+    const double tol = 0x1p-40 * largest;
+    __syncthreads();
+
+    uint64_t P = 0;                                                  // (uniform)
+    double x = 0.0;
+    uint32_t n = 0;
+    int32_t status = -1;                                             // the cap, unless step 2 finds nothing to admit
+    for (uint32_t outer = 0; outer <= cap; ++outer) {                // every outer step that goes on has factorised: it ends by `break`
+        // 2. the gradient of the lights outside P, the largest one enters
+        double w = r;
+        for (uint64_t m = P; m; m &= m - 1) {
+            const uint32_t j = (uint32_t)__builtin_ctzll(m);
+            w = w - A[j <= i ? i * S + j : j * S + i] * xs[j];
+        }
+        lane_val[i] = w;
+        __syncthreads();
+        double best = tol;
+        int32_t enter = -1;
+        for (uint32_t l = 0; l < L; ++l) {
+            const double v = lane_val[l];
+            if (!((P >> l) & 1ull) && v > best) {
+                best = v;
+                enter = (int32_t)l;
+            }
+        }
+        enter = __builtin_amdgcn_readfirstlane(enter);
+        __syncthreads();
+        if (enter < 0) {
+            status = 0;
+            break;
+        }
+        P |= 1ull << enter;
+        // 3. solve on P; step towards the solution until it is positive
+        bool positive = false;
+        while (n < cap) {
+            n += 1u;
+            const bool in = (P >> i) & 1ull;
+            int32_t bad = 0;
+            for (uint64_t mk = P; mk; mk &= mk - 1) {
+                const uint32_t k = (uint32_t)__builtin_ctzll(mk);
+                double s = 0.0;
+                if (in && i >= k) {
+                    s = A[i * S + k];
+                    for (uint64_t m = P & ((1ull << k) - 1ull); m; m &= m - 1) {
+                        const uint32_t mm = (uint32_t)__builtin_ctzll(m);
+                        s = s - A[mm * S + i] * A[mm * S + k];
+                    }
+                    if (i == k)
+                        piv = s;
+                }
+                __syncthreads();
+                const double pk = piv;
+                if (!(pk > 0.0 && pk < __builtin_huge_val())) {
+                    bad = (int32_t)k + 1;
+                    break;
+                }
+                const double d = sqrt(pk);
+                if (i == k)
+                    diag[k] = d;
+                else if (in && i > k)
+                    A[k * S + i] = s / d;
+                __syncthreads();
+            }
+            if (bad) {
+                if (row)
+                    rgb[(size_t)rig * L * 3u + (size_t)i * 3u + c] = __builtin_nanf("");
+                if (i == 0u) {
+                    info[rig * 3u + c] = bad;
+                    if (solves)
+                        solves[rig * 3u + c] = (int32_t)n;
+                }
+                return;
+            }
+            double y = r;
+            for (uint64_t mk = P; mk; mk &= mk - 1) {                // C z = r_P
+                const uint32_t k = (uint32_t)__builtin_ctzll(mk);
+                if (i == k)
+                    sol[k] = y / diag[k];
+                __syncthreads();
+                if (in && i > k)
+                    y = y - A[k * S + i] * sol[k];
+            }
+            if (in)
+                y = sol[i];
+            __syncthreads();
+            for (uint64_t mk = P; mk;) {                             // C^T s = z, from the last column
+                const uint32_t k = 63u - (uint32_t)__builtin_clzll(mk);
+                mk &= ~(1ull << k);
+                if (i == k)
+                    sol[k] = y / diag[k];
+                __syncthreads();
+                if (in && i < k)
+                    y = y - A[i * S + k] * sol[k];
+            }
+            const double s = in ? sol[i] : 0.0;
+            const uint64_t blocked = __ballot(in && !(s > 0.0));
+            if (blocked == 0ull) {
+                if (in)
+                    x = s;
+                xs[i] = x;
+                __syncthreads();
+                positive = true;
+                break;
+            }
+            lane_val[i] = x / (x - s);
+            __syncthreads();
+            uint32_t at = (uint32_t)__builtin_ctzll(blocked);
+            double alpha = lane_val[at];
+            for (uint64_t m = blocked & (blocked - 1); m; m &= m - 1) {
+                const uint32_t l = (uint32_t)__builtin_ctzll(m);
+                const double v = lane_val[l];
+                if (v < alpha) {
+                    alpha = v;
+                    at = l;
+                }
+            }
+            at = (uint32_t)__builtin_amdgcn_readfirstlane((int32_t)at);
+            if (in) {
+                const double step = s - x;
+                const double move = alpha * step;
+                x = x + move;
+            }
+            if (i == at)
+                x = 0.0;
+            const uint64_t leave = __ballot(in && !(x > 0.0));
+            if ((leave >> i) & 1ull)
+                x = 0.0;
+            P &= ~leave;
+            xs[i] = x;
+            __syncthreads();
+        }
+        if (!positive)                                               // n == cap
+            break;
+    }
+    if (row)
+        rgb[(size_t)rig * L * 3u + (size_t)i * 3u + c] = (float)x;
+    if (i == 0u) {
+        info[rig * 3u + c] = status;
+        if (solves)
+            solves[rig * 3u + c] = (int32_t)n;
+    }
 }
 
 template <int SLOTS>
@@ -323,5 +512,20 @@ extern "C" int gcfr_light_fit_solve(const double *gram, const double *rhs, int32
         return GCFR_ERR_INVALID_ARGUMENT;
     hipLaunchKernelGGL(light_fit_solve_kernel, dim3(3u, (uint32_t)rgb_batch), dim3(kSolveLanes), 0, (hipStream_t)stream, gram, rhs,
                        (uint32_t)B, (uint32_t)L, ridge, (uint32_t)rgb_batch, rgb, info);
+    return hipGetLastError() == hipSuccess ? GCFR_OK : GCFR_ERR_LAUNCH;
+}
+
+extern "C" int gcfr_light_fit_solve_nonneg(const double *gram, const double *rhs, int32_t B, int32_t L, double ridge, int32_t rgb_batch,
+                                           int32_t max_solves, float *rgb, int32_t *info, int32_t *solves, void *stream)
+{
+    if (!gram || !rhs || !rgb || !info || B < 1 || B > kFitMaxFaces || L < 1 || L > kFitMaxLights)
+        return GCFR_ERR_INVALID_ARGUMENT;
+    if (((uintptr_t)gram & 7u) || ((uintptr_t)rhs & 7u) || (rgb_batch != 1 && rgb_batch != B) || max_solves < 0)
+        return GCFR_ERR_INVALID_ARGUMENT;
+    if (!(ridge >= 0.0) || !std::isfinite(ridge))
+        return GCFR_ERR_INVALID_ARGUMENT;
+    const uint32_t cap = max_solves ? (uint32_t)max_solves : 3u * (uint32_t)L;
+    hipLaunchKernelGGL(light_fit_solve_nonneg_kernel, dim3(3u, (uint32_t)rgb_batch), dim3(kSolveLanes), 0, (hipStream_t)stream, gram,
+                       rhs, (uint32_t)B, (uint32_t)L, ridge, (uint32_t)rgb_batch, cap, rgb, info, solves);
     return hipGetLastError() == hipSuccess ? GCFR_OK : GCFR_ERR_LAUNCH;
 }

@@ -265,35 +265,38 @@ def relight_environment_frames(model, images, mask_u8, env, rotations, n_lights:
 
 @torch.no_grad()
 def capture_rig(model, reference_images, mask_u8, lights, ridge: float = 1e-3, shared: bool = False, ambient: float = 0.5,
-                focal: float = None, device="cuda", composite_mask_u8=None, epoch: int = 200) -> torch.Tensor:
+                focal: float = None, device="cuda", composite_mask_u8=None, epoch: int = 200, nonnegative: bool = False) -> torch.Tensor:
     """The rig `light_rgb` (B,L,3) -- (1,L,3) with `shared=True` -- of the photographs `reference_images` (B,H,W,3): the colour x
     weight of each of `lights` (L,3) | (B,L,3), 1 <= L <= 64, under which the model's own albedo and per-light shadings of a
     photograph come closest to that photograph inside the compositing mask.  ONE network pass (`forward_lights`) on the reference
     photographs, then `lighting.fit_light_rgb` on its albedo and final shading against the photographs themselves, weighted by the
     compositing mask (`composite_mask_u8`, or `mask_u8` where that is None; u8 / 255).  A device tensor, not differentiable, no
     host synchronisation; it is what `relight_rig(_device)` and `RelightSession(light_rgb=...)` take.  `ridge` / `shared`: see
-    `fit_light_rgb`, which also says why entries may be negative.  `model` / `ambient` / `focal` as in `relight_lights`."""
+    `fit_light_rgb`, which also says why entries may be negative; `nonnegative=True` fits under light_rgb >= 0 instead (see there).
+    `model` / `ambient` / `focal` as in `relight_lights`."""
     x = _as_batch(reference_images).to(device)
     n = (lights.shape if torch.is_tensor(lights) else np.asarray(lights).shape)
     L = n[-2] if len(n) >= 2 else 1
     if not 1 <= L <= MAX_FIT_LIGHTS:                                                  # a rig too large fails before the network pass
         raise GcfrError("capture_rig: 1 <= L <= %d lights; got %d" % (MAX_FIT_LIGHTS, L))
     out, cm, _transfer = _lights_pass(model, x, mask_u8, lights, ambient, focal, device, composite_mask_u8, epoch)
-    return fit_light_rgb(out[8], out[0], x, weight=cm.reshape(x.shape[1], x.shape[2]), ridge=ridge, shared=shared)
+    return fit_light_rgb(out[8], out[0], x, weight=cm.reshape(x.shape[1], x.shape[2]), ridge=ridge, shared=shared,
+                         nonnegative=nonnegative)
 
 
 @torch.no_grad()
 def rig_lighting_transfer(model, input_images, reference_images, mask_u8, lights, ridge: float = 1e-3, shared: bool = False,
                           ambient: float = 0.5, focal: float = None, device="cuda", fix_border: bool = False,
-                          composite_mask_u8=None, epoch: int = 200) -> torch.Tensor:
+                          composite_mask_u8=None, epoch: int = 200, nonnegative: bool = False) -> torch.Tensor:
     """"Light this face like that photograph", at the level of a rig: `capture_rig` on `reference_images[b]`, then
     `relight_rig_device` on `input_images[b]` with the captured rig -- (B,H,W,3) uint8 DEVICE composites, equal byte for byte to
     `relight_rig_device(model, input_images, mask_u8, lights, capture_rig(model, reference_images, mask_u8, lights, ...), ...)`
     given the same network outputs.  The counterpart of `lighting_transfer`, which reads ONE white light and one ambient from the
     network's lighting head: here `lights` (L,3) | (B,L,3) are fixed directions (a key / fill / rim set, `lighting.sphere_directions`)
     and their colours x weights come from the photograph.  Two network passes, one per set of photographs; with `shared=True` one
-    rig is fitted to all reference photographs and applied to every input."""
-    rgb = capture_rig(model, reference_images, mask_u8, lights, ridge, shared, ambient, focal, device, composite_mask_u8, epoch)
+    rig is fitted to all reference photographs and applied to every input.  `nonnegative` is `capture_rig`'s."""
+    rgb = capture_rig(model, reference_images, mask_u8, lights, ridge, shared, ambient, focal, device, composite_mask_u8, epoch,
+                      nonnegative)
     return relight_rig_device(model, input_images, mask_u8, lights, rgb, ambient, focal, device, fix_border, composite_mask_u8, epoch)
 
 

@@ -26,7 +26,8 @@ Rig capture (csrc/gcfr_light_fit.hip), the inverse of the rig stage: the `light_
 to a photograph, a weighted least-squares problem per face and channel -- "light this face like that photograph".
 
     light_normal_equations         the weighted Gram matrix and right-hand side over all pixels, f64 in a fixed order
-    fit_light_rgb                  the normal equations + a Cholesky solve with a relative ridge -> light_rgb (not differentiable)
+    fit_light_rgb                  the normal equations + a Cholesky solve with a relative ridge -> light_rgb (not differentiable);
+                                   `nonnegative=True`: the same system under light_rgb >= 0, by an active-set method
 """
 import math
 
@@ -400,7 +401,7 @@ def light_fit_geometry(B: int, H: int, W: int):
     return LIGHT_FIT_CHUNK, min(chunks, max(1, LIGHT_FIT_MAX_GROUPS // int(B)))
 
 
-def _check_fit(final_shading, albedo, image, weight, image_layout, out=None, shared=False, ridge=0.0):
+def _check_fit(final_shading, albedo, image, weight, image_layout, out=None, shared=False, ridge=0.0, max_solves=0):
     """Every shape, dtype, device and range BEFORE anything is launched or loaded: a mismatch never reaches the kernels."""
     named = [("final_shading", final_shading), ("albedo", albedo), ("image", image)] \
         + ([("weight", weight)] if weight is not None else []) + ([("out", out)] if out is not None else [])
@@ -431,6 +432,8 @@ def _check_fit(final_shading, albedo, image, weight, image_layout, out=None, sha
         raise _lib.GcfrError("weight must be (%d,%d,%d), (1,%d,%d) or (%d,%d); got %s" % (B, H, W, H, W, H, W, tuple(weight.shape)))
     if not (isinstance(ridge, (int, float)) and math.isfinite(ridge) and ridge >= 0.0):
         raise _lib.GcfrError("ridge must be a finite number >= 0; got %r" % (ridge,))
+    if isinstance(max_solves, bool) or not isinstance(max_solves, int) or not 0 <= max_solves < 2 ** 31:
+        raise _lib.GcfrError("max_solves must be an int >= 0 (0: the default cap, 3 L); got %r" % (max_solves,))
     if out is not None:
         rigs = 1 if shared else B
         if tuple(out.shape) != (rigs, L, 3) or not out.is_contiguous():
@@ -469,6 +472,15 @@ def _launch_fit_solve(gram, rhs, ridge, rgb, info):
                                                     info.data_ptr(), _lib.stream_ptr(dev)), "gcfr_light_fit_solve")
 
 
+def _launch_fit_solve_nonneg(gram, rhs, ridge, max_solves, rgb, info, solves):
+    B, _, L, _ = gram.shape
+    dev = gram.device
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().gcfr_light_fit_solve_nonneg(gram.data_ptr(), rhs.data_ptr(), B, L, float(ridge), rgb.shape[0], max_solves,
+                                                           rgb.data_ptr(), info.data_ptr(), solves.data_ptr(), _lib.stream_ptr(dev)),
+                   "gcfr_light_fit_solve_nonneg")
+
+
 def _normal_equations(final_shading, albedo, image, weight, image_layout):
     """light_normal_equations behind its checks"""
     B, L, _, _ = final_shading.shape
@@ -494,7 +506,8 @@ def light_normal_equations(final_shading: torch.Tensor, albedo: torch.Tensor, im
 
 
 def fit_light_rgb(final_shading: torch.Tensor, albedo: torch.Tensor, image: torch.Tensor, weight=None, ridge: float = 1e-3,
-                  shared: bool = False, image_layout: str = "nhwc", out=None, return_info: bool = False):
+                  shared: bool = False, image_layout: str = "nhwc", out=None, return_info: bool = False, nonnegative: bool = False,
+                  max_solves: int = 0):
     """The rig `light_rgb` (B,L,3) -- (1,L,3) with `shared=True`, one rig fitted to all faces -- under which `combine_lights`
     followed by the mask paste comes closest to the photograph `image`: per face and channel the weighted least-squares problem
         minimise  sum_p w (image_c - albedo_c sum_l x[l,c] final_shading[l])^2  +  ridge (trace(G_c) / L) |x[:,c]|^2
@@ -503,7 +516,15 @@ def fit_light_rgb(final_shading: torch.Tensor, albedo: torch.Tensor, image: torc
     and rounds once to f32; every operation's order is fixed (include/gcfr.h): equal inputs give equal bits.
     The default `ridge` is a convenience, not a gate: lights close to each other have nearly parallel shadings and make G
     ill-conditioned, the fit then trades large weights of opposite sign against each other, and the result MAY CONTAIN NEGATIVE
-    ENTRIES.  The rig stage allows them; there is no non-negative solver here.
+    ENTRIES.  The rig stage allows them, but such a rig reproduces its photograph only through cancellation, which does not survive
+    another face or a turned environment.
+    `nonnegative=True` solves the SAME system under light_rgb >= 0 (Lawson and Hanson's active-set method on the normal equations,
+    one launch in place of the Cholesky solve; order in include/gcfr.h): every entry is >= 0 (an excluded light is exactly +0), and
+    wherever the unconstrained solution is positive in every entry the two return the same bits.  It factorises once per step, at
+    the most `max_solves` times per rig and channel (0: the default cap, 3 L); `return_info=True` then returns
+    (light_rgb, info, solves), both (B|1,3) i32 on the device: info 0, or -1 where the cap was reached (the result is the current
+    iterate, still >= 0), or k + 1 where the pivot of light k was not a positive finite number (NaN entries); solves the number of
+    factorisations.  `max_solves` is not read without `nonnegative`, but is checked.
     `out`: a contiguous f32 buffer of the result's shape that the result is written into and which is returned --
     `RelightSession.light_rgb` between two replays, for example: a captured session is re-lit from a photograph without recapture.
     `return_info=True` returns (light_rgb, info): info (B|1,3) i32 ON THE DEVICE, 0 where the channel was solved, k + 1 where pivot k
@@ -511,12 +532,16 @@ def fit_light_rgb(final_shading: torch.Tensor, albedo: torch.Tensor, image: torc
     never synchronises with the host, so it cannot raise on a failed solve: look at `info`, or at the NaNs.
     NOT DIFFERENTIABLE: the inputs are detached and the result carries no graph.  A malformed input (rank, shape, dtype, device,
     L outside 1 .. 64, layout, `out`) raises GcfrError before anything is loaded or launched; host tensors raise too."""
-    _check_fit(final_shading, albedo, image, weight, image_layout, out, shared, ridge)
+    _check_fit(final_shading, albedo, image, weight, image_layout, out, shared, ridge, max_solves)
     B, L, _, _ = final_shading.shape
     dev = final_shading.device
     gram, rhs = _normal_equations(final_shading, albedo, image, weight, image_layout)
     rigs = 1 if shared else B
     rgb = torch.empty((rigs, L, 3), dtype=torch.float32, device=dev) if out is None else out
     info = torch.empty((rigs, 3), dtype=torch.int32, device=dev)
+    if nonnegative:
+        solves = torch.empty((rigs, 3), dtype=torch.int32, device=dev)
+        _launch_fit_solve_nonneg(gram, rhs, ridge, max_solves, rgb, info, solves)
+        return (rgb, info, solves) if return_info else rgb
     _launch_fit_solve(gram, rhs, ridge, rgb, info)
     return (rgb, info) if return_info else rgb

@@ -694,6 +694,39 @@ int gcfr_light_fit_normal(const float *final_shading, const float *albedo, const
 int gcfr_light_fit_solve(const double *gram, const double *rhs, int32_t B, int32_t L, double ridge, int32_t rgb_batch, float *rgb,
                          int32_t *info, void *stream);
 
+/*
+ * The NON-NEGATIVE solve, one launch, one workgroup per (rig, channel), on the same gram / rhs:
+ *   minimise  1/2 x^T A x - r^T x   subject to  x >= 0        A = G + ridge (trace(G) / L) I, r: exactly those of gcfr_light_fit_solve
+ * by Lawson and Hanson's active-set method on the normal equations.  Arguments, ranges, alignment and refusals as for
+ * gcfr_light_fit_solve; in addition max_solves >= 0 caps the factorisations per (rig, channel), 0 meaning the default cap 3 L, and
+ * solves (rgb_batch,3) i32 receives their number (NULL: not wanted).  Allocates nothing, never synchronises, may be captured.
+ * Order, all f64, one lane per sum, every product, sum, division and sqrt one IEEE operation:
+ *   1. x = 0; the passive set P empty; n = 0; tol = 2^-40 * max_l |r_l|  (an exact product; the maximum starts at 0 and takes |r_l|
+ *      where |r_l| > maximum, so a NaN never enters it).
+ *   2. for every l outside P:  w_l = r_l;  w_l = w_l - A[l,j] * x_j for j in P ascending.  j = the FIRST index with the largest w_l
+ *      among those with w_l > tol (comparisons are `>`: a NaN never wins).  None: finish, info 0.  Else j enters P.
+ *   3. if n == cap: finish, info -1.  Else n += 1 and solve A_PP s_P = r_P by the factorisation and substitutions of
+ *      gcfr_light_fit_solve restricted to the rows and columns in P, in ascending light index: column k in P gets
+ *      s_i = A[i,k]; s_i = s_i - C[i,m] * C[k,m] for m in P, m < k, ascending (rows i in P, i >= k); forward over k in P ascending,
+ *      back descending.  A pivot that is not a positive finite number: info = k + 1 (k the LIGHT's index), that channel's L entries
+ *      of rgb NaN, solves = n, finish.
+ *      If s_l > 0 for every l in P:  x_P = s_P, go to 2.
+ *      Else alpha and l* start as the quotient x_l / (x_l - s_l) and index of the first l in P with !(s_l > 0); a later such l
+ *      replaces them where its quotient `<` alpha (the first index wins a tie; a NaN quotient -- 0 / 0 -- never replaces, a first
+ *      one stays).  Then for l in P:  d = s_l - x_l;  m = alpha * d;  x_l = x_l + m  (three operations);  x_l* = 0;  every l in P
+ *      with !(x_l > 0) gets x_l = 0 and leaves P.  Repeat 3.
+ *   4. finishing with info 0 or -1:  rgb[., l, c] = (float)x_l, one rounding, a zero exactly +0;  solves[., c] = n.  Under info -1
+ *      x is the current iterate, feasible by construction.
+ * Consequences: every entry written is >= 0 or NaN.  Where the final passive set is all L lights, the last factorisation is
+ * operation for operation that of gcfr_light_fit_solve: wherever the unconstrained solution is positive in every entry the two
+ * entries return the same bits.  In exact arithmetic a newly admitted light has s_j > 0; where rounding makes it otherwise step 3
+ * removes it again with alpha = 0 and the cap ends the fit -- there is no extra rule.  Every loop is bounded by L, by the lights in
+ * P or by the cap, none by a floating-point condition: non-finite input ends within `cap` factorisations too (a NaN in r is never
+ * admitted: that light stays 0).
+ */
+int gcfr_light_fit_solve_nonneg(const double *gram, const double *rhs, int32_t B, int32_t L, double ridge, int32_t rgb_batch,
+                                int32_t max_solves, float *rgb, int32_t *info, int32_t *solves, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Measurement aid (bench.py `roofline.hbm_measured_copy_GBs`): a float4 grid-stride device-to-device copy of `bytes` bytes
  * (multiple of 16, both pointers 16-byte aligned), one workgroup of 256 lanes per CU, four loads in flight per lane, non-temporal --
