@@ -348,36 +348,32 @@ __device__ inline double fast_rsqrt64(double x)
 // more than a factor of two the differences carry f32 rounding (relative 6e-8 of the DIFFERENCE: a perturbation of the
 // surface, not of the normal's digits).  A non-finite cell poisons the same pixels as the convolution's taps do: every
 // neighbour is part of a or of b, the centre of every e.
-__device__ inline void unit_normal(const NormalsArgs &a, const float *z, int r, int c, float (&n)[3])
+//
+// In two halves, so that a caller can issue the nine loads long before it needs the normal (the march's epilogue: with every
+// other operand load, in front of its first store): load_depth_stencil() fetches the replicate-padded 3 x 3 neighbourhood,
+// row-major with the pixel itself at [4]; unit_normal_from() is the arithmetic on those nine values.
+__device__ inline void load_depth_stencil(int H, int W, const float *z, int r, int c, float (&v)[9])
 {
-#ifdef GCFR_R04_FIXED_COST
-    {
-        const Grad3 g = point_gradients(a, z, r, c);
-        const double nx = __builtin_fma(g.du[1], g.dv[2], -(g.du[2] * g.dv[1]));
-        const double ny = __builtin_fma(g.du[2], g.dv[0], -(g.du[0] * g.dv[2]));
-        const double nz = __builtin_fma(g.du[0], g.dv[1], -(g.du[1] * g.dv[0]));
-        const double n2sum = __builtin_fma(nz, nz, __builtin_fma(ny, ny, nx * nx));
-        double nn = n2sum > 1e-24 ? fast_sqrt64(n2sum) : 1e-12;
-        nn = nn > 1e-12 ? nn : 1e-12;
-        const double inv = fast_rcp64(nn);
-        n[0] = (float)(nx * inv);
-        n[1] = (float)(a.negate_y ? -(ny * inv) : (ny * inv));
-        n[2] = (float)(nz * inv);
-        return;
-    }
-#endif
-    const int W = a.W;
-    const bool has_l = c > 0, has_r = c < W - 1, has_u = r > 0, has_d = r < a.H - 1;
+    const bool has_l = c > 0, has_r = c < W - 1, has_u = r > 0, has_d = r < H - 1;
     // (raw buffer loads, byte offsets in 32 bits off one descriptor of the image's plane: no 64-bit address arithmetic per neighbour)
-    const __amdgpu_buffer_rsrc_t zr = make_rsrc(z, a.H * W * 4);
+    const __amdgpu_buffer_rsrc_t zr = make_rsrc(z, H * W * 4);
     const int b11 = (r * W + c) << 2, W4 = W << 2;
     const int bu = has_u ? b11 - W4 : b11, bd = has_d ? b11 + W4 : b11;
     const int ol = has_l ? 4 : 0, orr = has_r ? 4 : 0;
+    v[4] = buf_load_f32(zr, b11);
+    v[0] = buf_load_f32(zr, bu - ol), v[1] = buf_load_f32(zr, bu), v[2] = buf_load_f32(zr, bu + orr);
+    v[3] = buf_load_f32(zr, b11 - ol), v[5] = buf_load_f32(zr, b11 + orr);
+    v[6] = buf_load_f32(zr, bd - ol), v[7] = buf_load_f32(zr, bd), v[8] = buf_load_f32(zr, bd + orr);
+}
+__device__ inline void unit_normal_from(const NormalsArgs &a, const float (&v)[9], int r, int c, float (&n)[3])
+{
+    const int W = a.W;
+    const bool has_l = c > 0, has_r = c < W - 1, has_u = r > 0, has_d = r < a.H - 1;
     const float off = a.z_offset;
-    const float D11 = buf_load_f32(zr, b11) + off;  // depth + 1610 in f32 (T8:353)
-    const float e00 = (buf_load_f32(zr, bu - ol) + off) - D11, e01 = (buf_load_f32(zr, bu) + off) - D11, e02 = (buf_load_f32(zr, bu + orr) + off) - D11;
-    const float e10 = (buf_load_f32(zr, b11 - ol) + off) - D11, e12 = (buf_load_f32(zr, b11 + orr) + off) - D11;
-    const float e20 = (buf_load_f32(zr, bd - ol) + off) - D11, e21 = (buf_load_f32(zr, bd) + off) - D11, e22 = (buf_load_f32(zr, bd + orr) + off) - D11;
+    const float D11 = v[4] + off;  // depth + 1610 in f32 (T8:353)
+    const float e00 = (v[0] + off) - D11, e01 = (v[1] + off) - D11, e02 = (v[2] + off) - D11;
+    const float e10 = (v[3] + off) - D11, e12 = (v[5] + off) - D11;
+    const float e20 = (v[6] + off) - D11, e21 = (v[7] + off) - D11, e22 = (v[8] + off) - D11;
     const float h0 = e02 - e00, h1 = e12 - e10, h2 = e22 - e20;
     const float g0 = e20 - e00, g1 = e21 - e01, g2 = e22 - e02;
     const float a8 = __builtin_fmaf(2.0f, h1, h0 + h2), b8 = __builtin_fmaf(2.0f, g1, g0 + g2);  // (2 h exact: the fma rounds once, as the sum would)
@@ -399,6 +395,28 @@ __device__ inline void unit_normal(const NormalsArgs &a, const float *z, int r, 
     n[0] = (float)(nx * inv);
     n[1] = (float)(a.negate_y ? -(ny * inv) : (ny * inv));  // T8:354
     n[2] = (float)(nz * inv);
+}
+__device__ inline void unit_normal(const NormalsArgs &a, const float *z, int r, int c, float (&n)[3])
+{
+#ifdef GCFR_R04_FIXED_COST
+    {
+        const Grad3 g = point_gradients(a, z, r, c);
+        const double nx = __builtin_fma(g.du[1], g.dv[2], -(g.du[2] * g.dv[1]));
+        const double ny = __builtin_fma(g.du[2], g.dv[0], -(g.du[0] * g.dv[2]));
+        const double nz = __builtin_fma(g.du[0], g.dv[1], -(g.du[1] * g.dv[0]));
+        const double n2sum = __builtin_fma(nz, nz, __builtin_fma(ny, ny, nx * nx));
+        double nn = n2sum > 1e-24 ? fast_sqrt64(n2sum) : 1e-12;
+        nn = nn > 1e-12 ? nn : 1e-12;
+        const double inv = fast_rcp64(nn);
+        n[0] = (float)(nx * inv);
+        n[1] = (float)(a.negate_y ? -(ny * inv) : (ny * inv));
+        n[2] = (float)(nz * inv);
+        return;
+    }
+#endif
+    float v[9];
+    load_depth_stencil(a.H, a.W, z, r, c, v);
+    unit_normal_from(a, v, r, c, n);
 }
 
 // Backward of unit_normal() for one pixel, first half: (g0,g1,g2) = dLoss/d(unit normal output, y already negated)

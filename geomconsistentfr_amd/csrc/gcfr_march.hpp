@@ -1512,6 +1512,71 @@ __device__ GCFR_TILE_INLINE bool march_tile(ArgPtr a, const int bl, const int qy
     //  one use -- the last value the six-wave build spilled)
     float BCx_e = BCx;
     asm volatile("" : "+v"(BCx_e));
+// census: epilogue: pixel re-derivation, operand load batch
+    // Every operand the epilogue reads from memory is requested HERE, directly behind the sample loop and in front of the
+    // distance finish -- the scalar loads of the epilogue's arguments as one group, then the vector loads of the depth
+    // neighbourhood (or the normals handed in) and of the albedo -- and NO load follows a store: the output pointers carry no
+    // aliasing information, so a load written behind a store stays behind it, and vmcnt counts loads and stores together in
+    // issue order, so waiting for such a load also waits for every store in front of it to be acknowledged.  Written in the
+    // order store / load / use, the epilogue was a chain of seven serial memory round trips per wave (min_dist, stencil,
+    // normals_out, ambient, shading stores, three times albedo load -> multiply -> store) at the end of a wave's life, when it
+    // has nothing else in flight; now it is one wait for the slowest load, most of it hidden behind the distance finish, and
+    // then stores only.  (Not the hoist ABOVE the loop that DESIGN.md 4.1 rejects: here the loop's registers are dead.)
+    //
+    // The pixel's row / column / validity are RE-DERIVED here from a fresh lane id instead of being kept live across the
+    // sample loop: at the forced six waves per SIMD (80 VGPRs) they were exactly what the register allocator spilled
+    // (r, c and the 64-bit pixel index: 16-20 B of scratch per lane, stored before the loop and reloaded after it --
+    // cheap in time, but the scratch arena of every resident wave is written back to HBM once per launch: +15 MB).
+    // Lanes outside the image are clamped to (H - 1, W - 1): their loads stay inside the planes, and they leave before
+    // the first store.
+    const int lane_e = fresh_lane_id();
+    const int r_e = qy * TILE_H + lane_e / TILE_W, c_e = tx * TILE_W + (lane_e % TILE_W);
+    const bool valid_e = (r_e < H) && (c_e < W);
+    r = valid_e ? r_e : H - 1;
+    c = valid_e ? c_e : W - 1;
+    const size_t pix = (size_t)r * W + c;
+    const size_t o = (size_t)bl * P + pix;
+    const EpiPtr ep = launder((EpiPtr)&a->epi);
+    // scalar group (the kernel-argument segment; ambient[bl] is wave-uniform like the light point and read like it)
+    float *const min_dist = ep->min_dist;
+    int32_t *const argmin = WANT_ARGMIN ? ep->argmin : nullptr;
+    const float bonus = ep->bonus, bx_lo = ep->bx_lo, bx_hi = ep->bx_hi, by_lo = ep->by_lo, by_hi = ep->by_hi;
+    const float *const normals = FUSE_SHADE ? ep->normals : nullptr;
+    const float *const albedo = FUSE_SHADE ? ep->albedo : nullptr;
+    float *const shadow_w = FUSE_SHADE ? ep->shadow_w : nullptr, *const full = FUSE_SHADE ? ep->full : nullptr;
+    float *const final_shading = FUSE_SHADE ? ep->final_shading : nullptr, *const rendered = FUSE_SHADE ? ep->rendered : nullptr;
+    float *const normals_out = FUSE_SHADE ? ep->normals_out : nullptr;
+    const float intensity = FUSE_SHADE ? ep->intensity : 0.0f;
+    const float amb = FUSE_SHADE ? ((ConstF32Ptr)(unsigned long long)ep->ambient)[bl] : 0.0f;
+    NormalsArgs na = {};  // (field by field: the source lives in the constant address space)
+    float zs[9], n[3], alb[3];  // (zs or n: whichever the normals branch below loads)
+    if (FUSE_SHADE) {
+        na.H = H;
+        na.W = W;
+        na.inv_fx = ep->nrm.inv_fx;
+        na.inv_fy = ep->nrm.inv_fy;
+        na.cx = ep->nrm.cx;
+        na.cy = ep->nrm.cy;
+        na.z_offset = ep->nrm.z_offset;
+        na.negate_y = ep->nrm.negate_y;
+        // vector group
+        if (normals) {
+            const float *nrm_in = normals + (size_t)b * 3 * P + pix;
+            n[0] = nrm_in[0];
+            n[1] = nrm_in[P];
+            n[2] = nrm_in[2 * P];
+        } else {  // normals fused: the 3x3 depth neighbourhood of the stencil
+#ifndef GCFR_R04_FIXED_COST
+            load_depth_stencil(H, W, a->depth + (size_t)b * P, r, c, zs);
+#endif
+        }
+        const float *alb_in = albedo + (size_t)b * 3 * P + pix;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch)
+            alb[ch] = alb_in[ch * P];
+    }
+
+// census: epilogue: distance finish, tie, masked value, bonus
     // (sqrt_rn_normal: the correctly rounded square root for arguments >= 1e-4 -- both carry the reference's + 0.0001 -- see gcfr_device.hpp)
     const float den = sqrt_rn_normal(((BCx_e * BCx_e + BCy * BCy) + BCz * BCz) + kEps4);
     float d = sqrt_rn_normal(bestS) / den;
@@ -1551,73 +1616,56 @@ __device__ GCFR_TILE_INLINE bool march_tile(ArgPtr a, const int bl, const int qy
     }
     if (!finite_ray)  // (after the line above: a non-finite ray has no candidate range either, and is NaN with or without the option)
         d = __builtin_nanf("");
-    const EpiPtr ep = launder((EpiPtr)&a->epi);
-    const bool inside = (Cx >= ep->bx_lo) && (Cx <= ep->bx_hi) && (Cy >= ep->by_lo) && (Cy <= ep->by_hi);
+    const bool inside = (Cx >= bx_lo) && (Cx <= bx_hi) && (Cy >= by_lo) && (Cy <= by_hi);
     if (inside)
-        d = d + ep->bonus;
-// census: epilogue: pixel re-derivation, min_dist / argmin stores
-    // The pixel's row / column / validity are RE-DERIVED here from a fresh lane id instead of being kept live across the
-    // sample loop: at the forced six waves per SIMD (80 VGPRs) they were exactly what the register allocator spilled
-    // (r, c and the 64-bit pixel index: 16-20 B of scratch per lane, stored before the loop and reloaded after it --
-    // cheap in time, but the scratch arena of every resident wave is written back to HBM once per launch: +15 MB).
-    {
-        const int lane_e = fresh_lane_id();
-        const int r_e = qy * TILE_H + lane_e / TILE_W, c_e = tx * TILE_W + (lane_e % TILE_W);
-        const bool valid_e = (r_e < H) && (c_e < W);
-        r = valid_e ? r_e : H - 1;
-        c = valid_e ? c_e : W - 1;
-        if (!valid_e)
-            return false;
-    }
-    {
-        const size_t pix = (size_t)r * W + c;
-        const size_t o = (size_t)bl * P + pix;
-        ep->min_dist[o] = d;
-        if (WANT_ARGMIN)
-            ep->argmin[o] = besti;
-// census: epilogue: normals load / stencil call, normals_out store
-        if (FUSE_SHADE) {
-            float n[3];
-            const float *normals = ep->normals;
-            if (normals) {
-                const float *nrm = normals + (size_t)b * 3 * P + pix;
-                n[0] = nrm[0];
-                n[1] = nrm[P];
-                n[2] = nrm[2 * P];
-            } else {  // normals fused: 3x3 depth stencil, same device function as normals_fwd_kernel
-                NormalsArgs na = {};  // (field by field: the source lives in the constant address space)
-                na.H = H;
-                na.W = W;
-                na.inv_fx = ep->nrm.inv_fx;
-                na.inv_fy = ep->nrm.inv_fy;
-                na.cx = ep->nrm.cx;
-                na.cy = ep->nrm.cy;
-                na.z_offset = ep->nrm.z_offset;
-                na.negate_y = ep->nrm.negate_y;
-                unit_normal(na, a->depth + (size_t)b * P, r, c, n);
-                float *normals_out = ep->normals_out;
-                if (normals_out && l == 0) {
-                    float *no = normals_out + (size_t)b * 3 * P + pix;
-                    no[0] = n[0];
-                    no[P] = n[1];
-                    no[2 * P] = n[2];
-                }
+        d = d + bonus;
+    if (!valid_e)
+        return false;
+// census: epilogue: min_dist / argmin stores
+    // The inference kernels' outputs leave with NON-TEMPORAL stores: the march never reads them back, a batch writes 21 MB of them
+    // (8 faces x 256^2: ten planes) through an L2 of 4 MB per XCD whose hit rate on the texel / bounds gathers is 55 %, and with
+    // four batches in flight every line they displace is one a neighbouring wave's gather wanted.  Measured alone, interleaved
+    // (profiles/epilogue_loads_ab.txt): 34.74 -> 34.22 us per step.  The training kernels (WANT_ARGMIN) keep plain stores: their
+    // minimum distance, argmin and normals are re-read by the backward launch that follows.  (-DGCFR_EPI_NT=0: the A/B build.)
+#ifndef GCFR_EPI_NT
+#define GCFR_EPI_NT 1
+#endif
+    auto store = [](auto *p, auto v) {
+        if ((GCFR_EPI_NT != 0) && !WANT_ARGMIN)
+            __builtin_nontemporal_store(v, p);
+        else
+            *p = v;
+    };
+    store(min_dist + o, d);
+    if (WANT_ARGMIN)
+        store(argmin + o, besti);
+    if (FUSE_SHADE) {
+// census: epilogue: stencil call, normals_out store
+        if (!normals) {  // normals fused: same device function as normals_fwd_kernel
+#ifdef GCFR_R04_FIXED_COST
+            unit_normal(na, a->depth + (size_t)b * P, r, c, n);  // (the A/B build's stencil does its own loads)
+#else
+            unit_normal_from(na, zs, r, c, n);
+#endif
+            if (normals_out && l == 0) {
+                float *no = normals_out + (size_t)b * 3 * P + pix;
+                store(no, n[0]);
+                store(no + P, n[1]);
+                store(no + 2 * P, n[2]);
             }
-// census: epilogue: shading call, composite, stores (T8:517-522)
-            const Shaded sh = shade_pixel(x, y, zb, n[0], n[1], n[2], Cx, Cy, Cz, ep->ambient[bl], ep->intensity, d);
-            float *shadow_w = ep->shadow_w, *full = ep->full, *final_shading = ep->final_shading;
-            if (shadow_w)
-                shadow_w[o] = sh.w;
-            if (full)
-                full[o] = sh.full;
-            if (final_shading)
-                final_shading[o] = sh.fin;
-            const float *alb = ep->albedo + (size_t)b * 3 * P + pix;
-            float *ren = ep->rendered + (size_t)bl * 3 * P + pix;
-#pragma unroll
-            for (int ch = 0; ch < 3; ++ch)  // T8:519-522
-                ren[ch * P] = alb[ch * P] * sh.fin;
         }
+// census: epilogue: shading call, composite, stores (T8:517-522)
+        const Shaded sh = shade_pixel(x, y, zb, n[0], n[1], n[2], Cx, Cy, Cz, amb, intensity, d);
+        if (shadow_w)
+            store(shadow_w + o, sh.w);
+        if (full)
+            store(full + o, sh.full);
+        if (final_shading)
+            store(final_shading + o, sh.fin);
+        float *ren = rendered + (size_t)bl * 3 * P + pix;
+#pragma unroll
+        for (int ch = 0; ch < 3; ++ch)  // T8:519-522
+            store(ren + ch * P, alb[ch] * sh.fin);
     }
 // census: counters (counting build only)
 #ifdef GCFR_COUNTERS
