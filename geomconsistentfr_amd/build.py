@@ -25,7 +25,7 @@ SOURCES = ["gcfr_shadow.hip", "gcfr_shade.hip", "gcfr_backward.hip", "gcfr_norma
            "gcfr_dataset.hip", "gcfr_losses.hip", "gcfr_supervised_losses.hip", "gcfr_light_rig.hip", "gcfr_environment.hip",
            "gcfr_light_fit.hip"]
 MARCH_UNIT = "gcfr_march_unit.hip"
-# (tile width, samples per group): the default shape first -- it is the largest unit (it also holds the LDS-staged kernels)
+# (tile width, samples per group): the default shape first
 MARCH_UNITS = [(16, 4), (16, 2), (16, 1), (8, 4), (8, 2), (8, 1), (32, 4), (32, 2), (32, 1), (64, 4), (64, 2), (64, 1)]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fPIC", "-shared",
          "-fno-fast-math", "-munsafe-fp-atomics", "-Wall"]

@@ -55,10 +55,6 @@ __device__ inline void bwd_count_request(int src, const void *addr)
 
 #include "../../include/gcfr.h"
 
-#ifndef GCFR_BWD_INLINE
-#define GCFR_BWD_INLINE inline
-#endif
-
 namespace gcfr {
 
 __device__ inline double wave_sum(double v)
@@ -172,7 +168,7 @@ struct CornerScatter {  // the four bilinear-corner depth gradients of one argmi
     float val[4];
     int fy, fx, gy, gx;  // rows / columns of the corners (fy, fx after the -1 wrap): idx = {fy W + fx, fy W + gx, gy W + fx, gy W + gx}
 };
-__device__ GCFR_BWD_INLINE void shadow_bwd_pixel(const float *zimg, float *gz, const double *t_table, int H, int W,
+__device__ inline void shadow_bwd_pixel(const float *zimg, float *gz, const double *t_table, int H, int W,
                                         int r, int c, float Cx, float Cy, float Cz, int k, float g32,
                                         double (&gC)[3], double *own_depth_grad = nullptr,
                                         CornerScatter *defer = nullptr)
@@ -486,9 +482,6 @@ __device__ unsigned long long *g_bwd_trace = nullptr;
 #define GCFR_BWD1_WAVES_PER_EU 4
 #endif
 constexpr int kBwdTileW = 32, kBwdTileH = 8;  // 256 threads
-#ifndef GCFR_BWD_WINDOW
-#define GCFR_BWD_WINDOW 1
-#endif
 constexpr int kBwdWinW = 64, kBwdWinH = 48;  // the corner window: 64 columns (one lane each at the flush) x 48 rows of f32 = 12 KiB
 __global__ __launch_bounds__(256)
 __attribute__((amdgpu_waves_per_eu(GCFR_BWD1_WAVES_PER_EU, GCFR_BWD1_WAVES_PER_EU))) void render_bwd_single_light_kernel(ShadeBwdArgs a)
@@ -510,7 +503,6 @@ __attribute__((amdgpu_waves_per_eu(GCFR_BWD1_WAVES_PER_EU, GCFR_BWD1_WAVES_PER_E
     __shared__ double s_dd[6][256];
     __shared__ double s_part[4][4];
     double red[4] = {0.0, 0.0, 0.0, 0.0};  // dC.xyz, d ambient: accumulated over this workgroup's tiles
-#if GCFR_BWD_WINDOW
     // Corner window (round 4).  The four bilinear-corner gradients of a tile's 256 argmin samples are what the memory system
     // spends this kernel's time on: every atomic REQUEST (one per wave instruction and 64-B line touched) is a read-modify-write
     // at the memory side.  Neighbouring pixels' samples land on neighbouring -- often the same -- texels (parallel rays, similar
@@ -522,7 +514,6 @@ __attribute__((amdgpu_waves_per_eu(GCFR_BWD1_WAVES_PER_EU, GCFR_BWD1_WAVES_PER_E
     __shared__ int s_box[4][4];
     for (int i = (int)threadIdx.x; i < kBwdWinH * kBwdWinW; i += 256)
         s_win[i] = 0.0f;   // (every flush leaves the cells it read at zero again)
-#endif
 
 #ifdef GCFR_BWD_TRACE
     unsigned long long stamp[8] = {};
@@ -653,7 +644,6 @@ __attribute__((amdgpu_waves_per_eu(GCFR_BWD1_WAVES_PER_EU, GCFR_BWD1_WAVES_PER_E
         s_dd[q][threadIdx.x] = via_lds ? sg.ddu[q] : 0.0;
         s_dd[3 + q][threadIdx.x] = via_lds ? sg.ddv[q] : 0.0;
     }
-#if GCFR_BWD_WINDOW
     {   // this wave's corner box {r_min, c_min, -r_max, -c_max}; lanes without a sample do not count
         const bool hc = live && have_corners;
         const int big = 0x3fffffff;
@@ -666,7 +656,6 @@ __attribute__((amdgpu_waves_per_eu(GCFR_BWD1_WAVES_PER_EU, GCFR_BWD1_WAVES_PER_E
             s_box[threadIdx.x >> 6][3] = wc1;
         }
     }
-#endif
     GCFR_BWD_STAMP(3);
     __syncthreads();
     GCFR_BWD_STAMP(4);
@@ -693,7 +682,6 @@ __attribute__((amdgpu_waves_per_eu(GCFR_BWD1_WAVES_PER_EU, GCFR_BWD1_WAVES_PER_E
         GCFR_BWD_REQ(kReqOwnPixel, gz + p);
         atomicAdd(gz + p, (float)((ax * Sx + ay * Sy + Sz) + gzb));
     }
-#if GCFR_BWD_WINDOW
     // (wave-uniform: every thread reduces the four waves' boxes itself)
     const int box_r0 = min(min(s_box[0][0], s_box[1][0]), min(s_box[2][0], s_box[3][0]));
     const int box_c0 = min(min(s_box[0][1], s_box[1][1]), min(s_box[2][1], s_box[3][1]));
@@ -727,9 +715,7 @@ __attribute__((amdgpu_waves_per_eu(GCFR_BWD1_WAVES_PER_EU, GCFR_BWD1_WAVES_PER_E
                 }
             }
         }
-    } else
-#endif
-    if (true) {
+    } else {
     // The four bilinear-corner atomics of the argmin samples were 78 of this kernel's 167 us: neighbouring pixels march
     // nearly parallel rays, so at sample fraction t their samples are only (1 - t) texels apart and 2 ... 5 adjacent lanes
     // hit the SAME texel -- the L2 serialises those.  Runs of adjacent lanes (inside aligned groups of 8) with identical

@@ -206,12 +206,10 @@ __device__ inline int zb_log2_stride(int H, int W, int N, TablePtrT t_table, int
 
 // records per image: the tiles at the finest stride plus one sentinel (-inf, +inf) that uncovered footprints read
 __host__ __device__ inline int zb_max_tiles(int H, int W) { return ((H >> 3) + 1) * ((W >> 3) + 1) + 1; }
-// per-image stride of the records, a whole number of 1-KiB pieces: the march's LDS-staged variant copies an image's
-// records with global_load_lds_dwordx4, 64 lanes x 16 B per instruction
+// per-image stride of the records, a whole number of 1-KiB pieces (64 records).  History: the LDS-staged march of round 3
+// copied an image's records in 1-KiB pieces; that variant is gone, the padding is harmless and stays, because it is part of
+// every address the kernels compute from zb_stride() / zb_slot() and of what the committed profiles measured
 __host__ __device__ inline int zb_stride(int H, int W) { return (zb_max_tiles(H, W) + 63) & ~63; }
-// mask bitmap of the LDS-staged march: one bit per cell (1 = mask cell non-zero), row-major, 32 cells per dword,
-// per-mask stride padded to 1 KiB; needs W % 32 == 0
-__host__ __device__ inline int bitmap_stride_bytes(int H, int W) { return (((H * W) >> 3) + 1023) & ~1023; }
 // "horizon" tables of the trailing loop's termination test (build_horizon_block): per image four arrays of running maxima
 // {col_pre, col_suf, row_pre, row_suf} of the depth an unmasked sample can read, each kHorizonDim entries and CENTRED: entry
 // kHorizonDim/2 + X belongs to image-plane column X = c - W/2 (row entry kHorizonDim/2 - Y to Y = H/2 - r), entries outside the
@@ -303,7 +301,9 @@ struct ShadowQuadArgs {
     const int *mones;       // (MB,n_stat)  prepass output: 1 iff every mask cell of the chunk is non-zero
     int *tflag;             // [0] prepass output: 1 iff the sample table is increasing, inside [0,1] and uniform
     const uint8_t *mask;    // (MB,H,W)
-    const uint32_t *bitmap; // (MB, bitmap_stride_bytes / 4) prepass output (LDS-staged march): one bit per mask cell
+    const uint32_t *reserved0;  // always null, never read.  It was an operand of the LDS-staged march; it keeps the offsets of
+                                // the fields behind it: without it the compiler pairs the kernel-argument loads differently and
+                                // every march kernel's code changes (profiles/retire_lds_stage_device_code.txt)
     const float *light_pt;  // (B,L,3)
     const double *t_table;  // (N)
     unsigned long long *counters;  // GCFR_COUNTERS builds: work counts, see gcfr_options
@@ -478,39 +478,10 @@ __device__ inline ImageStats reduce_image_stats(ArgPtr a, int b, int lane, bool 
 //  all bit-identical, all slower: profiles/r02_schedule_experiments.md.  Their code was removed from the product source
 //  in round 3; it builds from commit 4db51f3 with -DGCFR_EXPERIMENTAL_SCHEDULES.  Round 3 added the one round 2 had left
 //  untried -- a budgeted first pass plus a second launch that resumes the unfinished tiles four ways from warm minima --
-//  measured it (bit-identical, 79-87 us against 68: profiles/r03_twopass_ab.md) and took it out again: commit 7e0eaa4.)
-#ifndef GCFR_TILE_INLINE
-#define GCFR_TILE_INLINE __forceinline__
-#endif
-
-// LDS image of the LDS-staged march (dynamic shared memory, sized by the launch): [mask bitmap, bitmap_stride_bytes |
-// depth-bounds records, zb_stride * 16 B] of the workgroup's image.  26 KiB at 256 x 256: six workgroups per CU, which is
-// what the march's forced occupancy (six waves per SIMD, four waves per workgroup) needs.
-extern __shared__ uint4 gcfr_lds_stage[];
-
-// Copy the image's bitmap (unless its mask has no zero cell: then the march never reads it) and bounds records into LDS:
-// 1-KiB pieces, piece i by wave i mod 4, each ONE global_load_lds_dwordx4 -- global -> LDS without passing through
-// registers, issued at kernel entry and awaited by the workgroup barrier in front of the sample loop, so the copy runs
-// behind the tile prologue's ~750 instructions.
-// census: LDS staging
-__device__ inline void stage_lds(ArgPtr a, int b, bool with_bitmap)
-{
-    const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-    const int H = a->H, W = a->W;
-    const int bm_bytes = bitmap_stride_bytes(H, W), zb_bytes = a->zb ? zb_stride(H, W) * 16 : 0;
-    const char *gbm = (const char *)a->bitmap + (size_t)(a->mask_batch == 1 ? 0 : b) * bm_bytes;
-    const char *gzb = (const char *)a->zb + (size_t)b * zb_slot(H, W) * 16;
-    const int n_bm = with_bitmap ? (bm_bytes >> 10) : 0, n_zb = zb_bytes >> 10;
-    for (int ch = wave; ch < n_bm + n_zb; ch += 4) {
-        const bool is_bm = ch < n_bm;
-        const int piece = is_bm ? ch : ch - n_bm;
-        const char *src = (is_bm ? gbm : gzb) + ((size_t)piece << 10) + (lane << 4);
-        const int dst = (is_bm ? 0 : bm_bytes) + (piece << 10);  // wave-uniform LDS byte offset; lane i lands at + 16 i
-        __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
-                                         (__attribute__((address_space(3))) void *)((__attribute__((address_space(3))) char *)gcfr_lds_stage + dst),
-                                         16, 0, 0);
-    }
-}
+//  measured it (bit-identical, 79-87 us against 68: profiles/r03_twopass_ab.md) and took it out again: commit 7e0eaa4.
+//  Round 3 also built an LDS-staged march -- the image's mask, one bit per cell, and its bounds records copied into LDS at kernel
+//  entry -- bit-identical and not faster: profiles/r03_lds_stage_ab.md.  It builds from commit 0b22e41; gcfr_options.lds_stage
+//  is still accepted and selects nothing.)
 // lane id from the hardware (two VALU), opaque to the optimiser: a value derived from it has no live range before this point
 // census: tile set-up: lane, pixel, descriptors, light, own depth
 __device__ inline int fresh_lane_id()
@@ -526,7 +497,7 @@ __device__ inline int fresh_lane_id()
 // every consumer of the reference multiplies them by the mask (T8:619, 633, 641, 643).  See include/gcfr.h.
 // MODE (round 4): what a tile does when it marches WITHOUT the depth bounds (it gave them up -- see the give-up test --, the
 // caller switched them off, or the sample table is not one they reason about).
-//   kModeInline  the loops below run with `use_zb` false (k-split and LDS-staged kernels);
+//   kModeInline  the loops below run with `use_zb` false (the k-split kernels);
 //   kModeFull    the tile RETURNS TRUE instead, before anything is marched or written, and the caller runs it again as
 //   kModeRough   the rough loop only: no bounds machinery compiled in at all.
 // The grid kernels hold both as sibling regions (march_grid): the rough loop inside the bounds variant, as a branch behind
@@ -534,9 +505,6 @@ __device__ inline int fresh_lane_id()
 // scratch in the six-wave kernel, reloaded at every test -- whereas separate instantiations do not interfere.  The price
 // is a second prologue (~5 % of a rough tile's work).
 enum { kModeInline = 0, kModeFull = 1, kModeRough = 2 };
-#ifndef GCFR_ROUGH
-#define GCFR_ROUGH 1
-#endif
 #ifndef GCFR_ROUGH_CHUNK
 #define GCFR_ROUGH_CHUNK 3      // samples in flight per iteration of the rough loop: six-wave inference march (round 4: 2 -- 3 spilled
                                 // then; since round 5's trims 3 and 4 fit the 80 registers: noise-400 faces +2.2 % / +0.7 %, the bench
@@ -545,16 +513,15 @@ enum { kModeInline = 0, kModeFull = 1, kModeRough = 2 };
 #ifndef GCFR_ROUGH_CHUNK_ARGMIN
 #define GCFR_ROUGH_CHUNK_ARGMIN 3   // ... five-wave training march
 #endif
-template <int TILE_W, bool EVEN_HALF, bool WANT_ARGMIN, int DEPTH, bool FUSE_SHADE, int SPLIT, bool ALL_ONES = false, bool LDS = false,
-          bool OWN = false, int MODE = kModeInline>
-__device__ GCFR_TILE_INLINE bool march_tile(ArgPtr a, const int bl, const int qy, const int tx,
+template <int TILE_W, bool EVEN_HALF, bool WANT_ARGMIN, int DEPTH, bool FUSE_SHADE, int SPLIT, bool ALL_ONES = false, bool OWN = false,
+          int MODE = kModeInline>
+__device__ __forceinline__ bool march_tile(ArgPtr a, const int bl, const int qy, const int tx,
                                            const ImageStats &st)
 {
-    static_assert(MODE == kModeInline || (SPLIT == 0 && !LDS), "full / rough pairs: the grid schedule's global-memory kernels");
+    static_assert(MODE == kModeInline || SPLIT == 0, "full / rough pairs: the grid schedule's kernels");
     constexpr int TILE_H = 64 / TILE_W;
     static_assert(SPLIT == 0 || SPLIT == 1, "SPLIT: 0 = one wave per tile, 1 = the workgroup's four waves split the sample range");
-    static_assert(!(LDS && SPLIT != 0), "the LDS-staged march is a throughput variant: one wave per tile");
-    static_assert(!(OWN && (LDS || SPLIT != 0 || ALL_ONES)), "pixels = mask: the grid schedule's global-memory variant only");
+    static_assert(!(OWN && (SPLIT != 0 || ALL_ONES)), "pixels = mask: the grid schedule only");
 // census: tile set-up: lane, pixel, descriptors, light, own depth
     const int H = a->H, W = a->W, L = a->L;
     // Wave-uniform read-only inputs are read through the CONSTANT address space: in the persistent schedule the
@@ -567,27 +534,15 @@ __device__ GCFR_TILE_INLINE bool march_tile(ArgPtr a, const int bl, const int qy
     typedef const __attribute__((address_space(4))) float *ConstF32Ptr;
     typedef const __attribute__((address_space(4))) int *ConstI32Ptr;
     const TablePtr tt = (TablePtr)(unsigned long long)a->t_table;
-#ifndef GCFR_FRESH_LANE
-#define GCFR_FRESH_LANE 1
-#endif
     // (a kernel holds two instantiations of this function -- all-ones masks or not -- one after the other: computed from
     //  threadIdx the pixel's row / column are common subexpressions of both, hoisted in front of the first and kept alive
     //  across it for the second; a lane id the optimiser cannot see through is re-derived by each)
-    const int lane = (GCFR_FRESH_LANE != 0) ? fresh_lane_id() : (int)(threadIdx.x & 63);
+    const int lane = fresh_lane_id();
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     // sample range of this wave
     constexpr bool KSPLIT = SPLIT == 1;
-#ifndef GCFR_TRAIL
-#define GCFR_TRAIL 1
-#endif
-#ifndef GCFR_HORIZON
-#define GCFR_HORIZON 1
-#endif
-#ifndef GCFR_TRAIL_ALL_ONES
-#define GCFR_TRAIL_ALL_ONES 1
-#endif
-    // the trailing loop, see the sample loop (all-ones masks: there is no mask work to save, but its termination test is the sharper one)
-    constexpr bool TRAIL = (GCFR_TRAIL != 0) && !KSPLIT && !LDS && (!ALL_ONES || (GCFR_TRAIL_ALL_ONES != 0));
+    // the trailing loop, see the sample loop (all-ones masks too: there is no mask work to save, but its termination test is the sharper one)
+    constexpr bool TRAIL = !KSPLIT;
     constexpr bool ROUGH = MODE == kModeRough;  // the rough loop, see the sample loops
     const int chunk = KSPLIT ? (a->N + 3) >> 2 : a->N;
     const int k_lo = KSPLIT ? wave * chunk : 0;
@@ -687,13 +642,8 @@ __device__ GCFR_TILE_INLINE bool march_tile(ArgPtr a, const int bl, const int qy
     // (v_sqrt_f32 / v_rcp_f32, 1 ulp each: n and c1 only ever enter the BOUNDS -- the give-up heuristic, Kerr, the skip and the
     //  termination tests -- whose error terms K1 = ... + 1e-6 |c1| t and K2 r = (1e-6 n + ...) r budget sixteen ulp for each; the
     //  IEEE square root and division cost 27 instructions more per tile, round 5's census)
-#ifdef GCFR_R04_FIXED_COST
-    const float nrm = __builtin_sqrtf(BCx * BCx + BCy * BCy);
-    const float c1 = BCz * ((dxf * BCx + dyf * BCy) / nrm);
-#else
     const float nrm = __builtin_amdgcn_sqrtf(BCx * BCx + BCy * BCy);
     const float c1 = BCz * ((dxf * BCx + dyf * BCy) * __builtin_amdgcn_rcpf(nrm));
-#endif
     // (round 4: the give-up test sits in FRONT of the candidate-range computation -- a tile that hands itself to the rough
     //  variant has then paid for the end point and this test only, not for the box / octagon clipping it would do twice)
     const float t_abs = __builtin_bit_cast(float, tfl[kTfTabs]);  // max(|tt[0]|, |tt[N-1]|)
@@ -905,22 +855,6 @@ __device__ GCFR_TILE_INLINE bool march_tile(ArgPtr a, const int bl, const int qy
         }
         return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(zr, off, 0, 0));
     };
-    // the same record from the workgroup's LDS copy (bitmap first, records behind it)
-    const int lds_zb_base = bitmap_stride_bytes(H, W);
-    auto lds_load_b32 = [&](int byte_off) -> uint32_t {
-        return *(const __attribute__((address_space(3))) uint32_t *)((__attribute__((address_space(3))) const char *)gcfr_lds_stage + byte_off);
-    };
-    auto lds_zb_fetch = [&](int ca, int ra, int cb, int rb) -> f32x4 {
-        const int cmin = min(ca, cb), cmax = max(ca, cb), rmin = min(ra, rb), rmax = max(ra, rb);
-        const int tj = cmin >> zls, ti = rmin >> zls;
-        int off = (__mul24(ti, zntw) + tj) << 4;
-        if (!zb_trusted) {  // (wave-uniform branch)
-            const bool covered = (cmin >= 0) && (rmin >= 0) && (cmax <= W - 1) && (rmax <= H - 1) &&
-                                 (cmax + 2 <= ((tj + 2) << zls) - 1) && (rmax + 2 <= ((ti + 2) << zls) - 1);
-            off = covered ? off : zb_sentinel;
-        }
-        return *(const __attribute__((address_space(3))) f32x4 *)((__attribute__((address_space(3))) const char *)gcfr_lds_stage + lds_zb_base + off);
-    };
 
 // census: loop: mask prefetch (positions, rint, gathers)
     // Two-stage software pipeline.  Stage A (sample k+1): position, rounded cell, issue the mask byte
@@ -1093,7 +1027,7 @@ __device__ GCFR_TILE_INLINE bool march_tile(ArgPtr a, const int bl, const int qy
     };
 // census: loop: sample body (bilinear, distance, minimum)
     // consume(): what happens to one group once its mask values `cm` (0 = masked) are known.  LAZY = false: `cz` is the
-    // group's bounds record, tested here if some lane has an unmasked sample; LAZY = true (LDS-staged variant): the
+    // group's bounds record, tested here if some lane has an unmasked sample; LAZY = true (the trailing loop): the
     // caller has tested it already and passes the lane's verdict in `cw_in`.  ta64 / tb64: the group's first / last
     // table value; tn64: the next group's first one.
     // One sample's arithmetic behind its texel gather: bilinear depth (T8:480-494, f64), point A (T8:497-502), the squared
@@ -1225,81 +1159,7 @@ __device__ GCFR_TILE_INLINE bool march_tile(ArgPtr a, const int bl, const int qy
         return consume(k0, cur.m, cur.z, ta64, tb64, tc0, check_finished, std::false_type{}, false);
     };
 
-// census: loop: LDS-staged variant
-    // LDS-staged variant (round 3).  The workgroup's image -- its mask as a BITMAP and its depth-bounds
-    // records -- was copied into LDS by the four waves at kernel entry (stage_lds, global_load_lds_dwordx4); what the
-    // global variant gathers one group ahead through the texture path (four 1-byte mask gathers, each occupying the
-    // addressers like a full-width load, and one 16-byte record per lane) is here four ds_read_b32 + one ds_read_b128 of
-    // the group ITSELF: LDS answers in ~100 cycles, so there is no second register buffer and no two-groups-ahead table
-    // bookkeeping, and the texture path carries only the bodies' texel gathers.  Same cells, same records, same
-    // arithmetic after them: bit-identical.
-    auto group_lds = [&](int k0, bool check_finished) -> bool {
-        const double ta64 = tq[0], tb64 = tq[DEPTH - 1];  // (tq holds THIS group's table values)
-        uint32_t cm[DEPTH];
-        int cj[DEPTH], rj[DEPTH], cell[DEPTH];
-        GCFR_COUNT(kCntGroupsVisited, 1);
-        // (1) the bounds test FIRST: it needs the first and the last sample's cells only.  The mask decides nothing for a
-        //     lane that cannot win AND already holds a minimum that is certainly below the masked value 1e6 (bestS <
-        //     safeS: its `any_masked` no longer matters, see the early termination) -- if that is every lane of the wave,
-        //     the group is over without a single mask lookup: the two middle positions, the four bitmap reads and the
-        //     mask bookkeeping are never computed.  Only the LDS variant can order it this way: the global variant has to
-        //     start its mask gathers a group ahead, before it knows anything.
-        bool cw = false;
-        if (use_zb) {
-            double px, py;
-            pos_tq(0, px, py);
-            cell[0] = mask_offset(px, py, cj[0], rj[0]);
-            pos_tq(DEPTH - 1, px, py);
-            cell[DEPTH - 1] = mask_offset(px, py, cj[DEPTH - 1], rj[DEPTH - 1]);
-            const f32x4 cz = lds_zb_fetch(cj[0], rj[0], cj[DEPTH - 1], rj[DEPTH - 1]);
-            cw = bound_cw(cz, ta64, tb64, k0);
-            if (__builtin_amdgcn_ballot_w64(!(cw && (bestS < safeS))) == 0ull) {
-#ifdef GCFR_AUDIT
-                audit_safe(cw);
-#endif
-                load_tq(k0 + DEPTH);
-                return finish_check(k0, tq[0], check_finished);
-            }
-        }
-        // (2) some lane may still win (or has no minimum yet): the group's mask bits, then the bodies
-        if (ALL_ONES) {
-#pragma unroll
-            for (int j = 0; j < DEPTH; ++j)
-                cm[j] = 1u;
-        } else {
-#pragma unroll
-            for (int j = 0; j < DEPTH; ++j) {
-                if (!(use_zb && (j == 0 || j == DEPTH - 1))) {
-                    double px, py;
-                    pos_tq(j, px, py);
-                    cell[j] = mask_offset(px, py, cj[j], rj[j]);  // row * W + col; W % 32 == 0: 32 cells of a row per dword
-                }
-                cm[j] = lds_load_b32((cell[j] >> 3) & ~3);
-            }
-        }
-        load_tq(k0 + DEPTH);           // the next group's table values (scalar loads, answered while this group runs)
-        if (!ALL_ONES) {
-#pragma unroll
-            for (int j = 0; j < DEPTH; ++j)
-                cm[j] = __builtin_amdgcn_ubfe(cm[j], (uint32_t)cj[j], 1u);  // bit (col mod 32): the offset operand uses 5 bits
-        }
-        return consume(k0, cm, f32x4{}, ta64, tb64, tq[0], check_finished, std::true_type{}, cw);
-    };
-
-// census: loop: LDS-staged variant
-    if (LDS) {
-        __syncthreads();  // the staged image is complete (every wave of the workgroup gets here exactly once)
-        if (k_begin < k_end)
-            load_tq(k_begin);
-        for (int k0 = k_begin; k0 < k_end; k0 += 2 * DEPTH) {
-            if (!group_lds(k0, false))
-                break;
-            if (k0 + DEPTH >= k_end)
-                break;
-            if (!group_lds(k0 + DEPTH, true))
-                break;
-        }
-    } else if (ROUGH) {
+    if (ROUGH) {
 // census: loop: rough loop
         // Rough loop (round 4).  A tile that marches WITHOUT the depth bounds -- it gave them up (a surface rougher than its
         // rays rise: an untrained network's depth, 7,259 of 8,192 tiles at noise amplitude 400), the caller switched them off, or
@@ -1413,7 +1273,7 @@ __device__ GCFR_TILE_INLINE bool march_tile(ArgPtr a, const int bl, const int qy
             load_tq(k0 + 2 * DEPTH);
             const bool check = (((k0 - k_trail) / DEPTH) & 1) != 0;  // every other group, as in the main loop (every group: measured level, -0.5 %)
             // (the tables' offset is read from the kernel arguments at every use -- a scalar load -- rather than kept in a register)
-            const int hz_off = (GCFR_HORIZON != 0) && check && (k0 + DEPTH < k_end) ? launder(a)->hz_off : -1;
+            const int hz_off = check && (k0 + DEPTH < k_end) ? launder(a)->hz_off : -1;
             const bool check_hz = hz_off >= 0;
             const float tn = (float)tc0;  // the next group's first table value
             const bool cw = bound_cw(zcur, ta64, tb64, k0);
@@ -1566,9 +1426,7 @@ __device__ GCFR_TILE_INLINE bool march_tile(ArgPtr a, const int bl, const int qy
             n[1] = nrm_in[P];
             n[2] = nrm_in[2 * P];
         } else {  // normals fused: the 3x3 depth neighbourhood of the stencil
-#ifndef GCFR_R04_FIXED_COST
             load_depth_stencil(H, W, a->depth + (size_t)b * P, r, c, zs);
-#endif
         }
         const float *alb_in = albedo + (size_t)b * 3 * P + pix;
 #pragma unroll
@@ -1626,12 +1484,9 @@ __device__ GCFR_TILE_INLINE bool march_tile(ArgPtr a, const int bl, const int qy
     // (8 faces x 256^2: ten planes) through an L2 of 4 MB per XCD whose hit rate on the texel / bounds gathers is 55 %, and with
     // four batches in flight every line they displace is one a neighbouring wave's gather wanted.  Measured alone, interleaved
     // (profiles/epilogue_loads_ab.txt): 34.74 -> 34.22 us per step.  The training kernels (WANT_ARGMIN) keep plain stores: their
-    // minimum distance, argmin and normals are re-read by the backward launch that follows.  (-DGCFR_EPI_NT=0: the A/B build.)
-#ifndef GCFR_EPI_NT
-#define GCFR_EPI_NT 1
-#endif
+    // minimum distance, argmin and normals are re-read by the backward launch that follows.
     auto store = [](auto *p, auto v) {
-        if ((GCFR_EPI_NT != 0) && !WANT_ARGMIN)
+        if (!WANT_ARGMIN)
             __builtin_nontemporal_store(v, p);
         else
             *p = v;
@@ -1642,11 +1497,7 @@ __device__ GCFR_TILE_INLINE bool march_tile(ArgPtr a, const int bl, const int qy
     if (FUSE_SHADE) {
 // census: epilogue: stencil call, normals_out store
         if (!normals) {  // normals fused: same device function as normals_fwd_kernel
-#ifdef GCFR_R04_FIXED_COST
-            unit_normal(na, a->depth + (size_t)b * P, r, c, n);  // (the A/B build's stencil does its own loads)
-#else
             unit_normal_from(na, zs, r, c, n);
-#endif
             if (normals_out && l == 0) {
                 float *no = normals_out + (size_t)b * 3 * P + pix;
                 store(no, n[0]);
@@ -1712,7 +1563,7 @@ __device__ GCFR_TILE_INLINE bool march_tile(ArgPtr a, const int bl, const int qy
 
 // Grid schedule: one workgroup = four horizontally adjacent tiles (one per wave), 3-D grid x = tile-quad column,
 // y = tile row, z = (image, light) -- no integer divisions, dispatch order image-major with row-major tiles.
-template <int TILE_W, bool EVEN_HALF, bool WANT_ARGMIN, int DEPTH, bool FUSE_SHADE, bool LDS = false, bool OWN = false>
+template <int TILE_W, bool EVEN_HALF, bool WANT_ARGMIN, int DEPTH, bool FUSE_SHADE, bool OWN = false>
 __device__ __forceinline__ void march_grid(ArgPtr a)
 {
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -1720,21 +1571,15 @@ __device__ __forceinline__ void march_grid(ArgPtr a)
     const int bl = a->bl_offset + (int)blockIdx.z;
     const bool want_z = (a->zb != nullptr);
     const ImageStats st = reduce_image_stats(a, bl / a->L, threadIdx.x & 63, want_z);
-    if (LDS)
-        stage_lds(a, bl / a->L, st.mask_all_ones == 0);  // every wave of the workgroup copies its share, tile or no tile
-    if (tx >= a->tiles_x) {
-        if (LDS)
-            __syncthreads();  // (the barrier the marching waves pass in front of their sample loop)
-        return;  // (without LDS staging the waves of a workgroup never synchronise)
-    }
+    if (tx >= a->tiles_x)
+        return;  // (the waves of a workgroup never synchronise)
     // (the all-ones test is wave-uniform -- a fact about the mask, valid for any sample table; no pixel is outside such a mask)
-    constexpr int FULL = (LDS || GCFR_ROUGH == 0) ? kModeInline : kModeFull;
     bool rough;
     if (st.mask_all_ones != 0)
-        rough = march_tile<TILE_W, EVEN_HALF, WANT_ARGMIN, DEPTH, FUSE_SHADE, 0, true, LDS, false, FULL>(a, bl, (int)blockIdx.y, tx, st);
+        rough = march_tile<TILE_W, EVEN_HALF, WANT_ARGMIN, DEPTH, FUSE_SHADE, 0, true, false, kModeFull>(a, bl, (int)blockIdx.y, tx, st);
     else
-        rough = march_tile<TILE_W, EVEN_HALF, WANT_ARGMIN, DEPTH, FUSE_SHADE, 0, false, LDS, OWN, FULL>(a, bl, (int)blockIdx.y, tx, st);
-    if (FULL == kModeFull && GCFR_M(15, false &&, ) __builtin_amdgcn_readfirstlane((int)rough) != 0) {  // the tile marches without the depth bounds
+        rough = march_tile<TILE_W, EVEN_HALF, WANT_ARGMIN, DEPTH, FUSE_SHADE, 0, false, OWN, kModeFull>(a, bl, (int)blockIdx.y, tx, st);
+    if (GCFR_M(15, false &&, ) __builtin_amdgcn_readfirstlane((int)rough) != 0) {  // the tile marches without the depth bounds
         // (the image statistics are reduced AGAIN, through a laundered pointer -- a dozen scalar loads: kept alive across the
         //  bounds variant for this call they were eleven more SGPRs than the kernel has, spilled into a VGPR's lanes for the
         //  whole kernel: one register less in the main loops and a v_readlane at every use, -1.2 % on the bench faces)
@@ -1744,9 +1589,9 @@ __device__ __forceinline__ void march_grid(ArgPtr a)
         const int bl2 = WANT_ARGMIN ? bl : a2->bl_offset + (int)blockIdx.z;
         const ImageStats st2 = WANT_ARGMIN ? st : reduce_image_stats(a2, bl2 / a2->L, threadIdx.x & 63, false);
         if (st2.mask_all_ones != 0)
-            march_tile<TILE_W, EVEN_HALF, WANT_ARGMIN, DEPTH, FUSE_SHADE, 0, true, false, false, kModeRough>(a2, bl2, (int)blockIdx.y, tx, st2);
+            march_tile<TILE_W, EVEN_HALF, WANT_ARGMIN, DEPTH, FUSE_SHADE, 0, true, false, kModeRough>(a2, bl2, (int)blockIdx.y, tx, st2);
         else
-            march_tile<TILE_W, EVEN_HALF, WANT_ARGMIN, DEPTH, FUSE_SHADE, 0, false, false, OWN, kModeRough>(a2, bl2, (int)blockIdx.y, tx, st2);
+            march_tile<TILE_W, EVEN_HALF, WANT_ARGMIN, DEPTH, FUSE_SHADE, 0, false, OWN, kModeRough>(a2, bl2, (int)blockIdx.y, tx, st2);
     }
 }
 
@@ -1754,11 +1599,11 @@ __device__ __forceinline__ void march_grid(ArgPtr a)
 //  names of rounds 1-2 in profiles and tools: shadow_fwd_quad_kernel<16, true, 4, true, 0>.)
 enum { kSchedGrid = 0 };
 
-template <int SCHED, int TILE_W, bool EVEN_HALF, bool WANT_ARGMIN, int DEPTH, bool FUSE_SHADE, bool LDS = false, bool OWN = false>
+template <int SCHED, int TILE_W, bool EVEN_HALF, bool WANT_ARGMIN, int DEPTH, bool FUSE_SHADE, bool OWN = false>
 __device__ __forceinline__ void march_dispatch()
 {
     static_assert(SCHED == kSchedGrid, "the product library has the grid schedule only");
-    march_grid<TILE_W, EVEN_HALF, WANT_ARGMIN, DEPTH, FUSE_SHADE, LDS, OWN>(kernel_args());
+    march_grid<TILE_W, EVEN_HALF, WANT_ARGMIN, DEPTH, FUSE_SHADE, OWN>(kernel_args());
 }
 
 template <int TILE_W, bool EVEN_HALF, int DEPTH, bool FUSE_SHADE, int SCHED>
@@ -1778,19 +1623,6 @@ template <int TILE_W, bool EVEN_HALF, int DEPTH, bool FUSE_SHADE, int SCHED>
 __global__ __launch_bounds__(256)
 __attribute__((amdgpu_waves_per_eu(GCFR_MARCH_ARGMIN_WAVES_PER_EU, GCFR_MARCH_ARGMIN_WAVES_PER_EU))) void shadow_fwd_quad_argmin_own_kernel(ShadowQuadArgs)
 {
-    march_dispatch<SCHED, TILE_W, EVEN_HALF, true, DEPTH, FUSE_SHADE, false, true>();
-}
-// LDS-staged variants (see group_lds in march_tile): the same kernels with the image's mask bitmap and bounds records in LDS
-template <int TILE_W, bool EVEN_HALF, int DEPTH, bool FUSE_SHADE, int SCHED>
-__global__ __launch_bounds__(256)
-__attribute__((amdgpu_waves_per_eu(GCFR_MARCH_WAVES_PER_EU, GCFR_MARCH_WAVES_PER_EU))) void shadow_fwd_quad_lds_kernel(ShadowQuadArgs)
-{
-    march_dispatch<SCHED, TILE_W, EVEN_HALF, false, DEPTH, FUSE_SHADE, true>();
-}
-template <int TILE_W, bool EVEN_HALF, int DEPTH, bool FUSE_SHADE, int SCHED>
-__global__ __launch_bounds__(256)
-__attribute__((amdgpu_waves_per_eu(GCFR_MARCH_ARGMIN_WAVES_PER_EU, GCFR_MARCH_ARGMIN_WAVES_PER_EU))) void shadow_fwd_quad_argmin_lds_kernel(ShadowQuadArgs)
-{
     march_dispatch<SCHED, TILE_W, EVEN_HALF, true, DEPTH, FUSE_SHADE, true>();
 }
 // k-split (tiny launches, one or two images): latency-bound, four gathers in flight per body, occupancy as it falls;
@@ -1808,28 +1640,12 @@ __global__ __launch_bounds__(256) void shadow_fwd_quad_ksplit_kernel(ShadowQuadA
 // ----------------------------------------------------------------------------------------------
 // launchers: pick the kernel for (parity of W/2 and H/2, argmin wanted, schedule) and enqueue it
 // ----------------------------------------------------------------------------------------------
-enum Schedule { kGrid = kSchedGrid, kKSplit, kGridLds, kGridOwn };
+enum Schedule { kGrid = kSchedGrid, kKSplit, kGridOwn };
 
 template <int TILE_W, int DEPTH, bool FUSE>
-static void launch_quad4(const ShadowQuadArgs &a, bool even_half, bool want_argmin, Schedule sch, dim3 grid,
-                         hipStream_t st, unsigned lds_bytes)
+static void launch_quad4(const ShadowQuadArgs &a, bool even_half, bool want_argmin, Schedule sch, dim3 grid, hipStream_t st)
 {
 #define GCFR_LAUNCH(KERNEL, ...) hipLaunchKernelGGL((KERNEL<TILE_W, __VA_ARGS__>), grid, dim3(256), 0, st, a)
-#define GCFR_LAUNCH_LDS(KERNEL, ...) hipLaunchKernelGGL((KERNEL<TILE_W, __VA_ARGS__>), grid, dim3(256), lds_bytes, st, a)
-#define GCFR_LAUNCH_SCHED(SCHED)                                                    \
-    do {                                                                            \
-        if (even_half) {                                                            \
-            if (want_argmin)                                                        \
-                GCFR_LAUNCH(shadow_fwd_quad_argmin_kernel, true, DEPTH, FUSE, SCHED);  \
-            else                                                                    \
-                GCFR_LAUNCH(shadow_fwd_quad_kernel, true, DEPTH, FUSE, SCHED);      \
-        } else {                                                                    \
-            if (want_argmin)                                                        \
-                GCFR_LAUNCH(shadow_fwd_quad_argmin_kernel, false, DEPTH, FUSE, SCHED); \
-            else                                                                    \
-                GCFR_LAUNCH(shadow_fwd_quad_kernel, false, DEPTH, FUSE, SCHED);     \
-        }                                                                           \
-    } while (0)
     if (sch == kKSplit) {
         if (even_half) {
             if (want_argmin)
@@ -1842,52 +1658,44 @@ static void launch_quad4(const ShadowQuadArgs &a, bool even_half, bool want_argm
             else
                 GCFR_LAUNCH(shadow_fwd_quad_ksplit_kernel, false, false, DEPTH, FUSE);
         }
-    } else if (sch == kGridLds) {
-        if constexpr (TILE_W == 16 && DEPTH == 4) {  // (the default shape: the one the LDS-staged kernels are built for)
-            if (even_half) {
-                if (want_argmin)
-                    GCFR_LAUNCH_LDS(shadow_fwd_quad_argmin_lds_kernel, true, DEPTH, FUSE, kSchedGrid);
-                else
-                    GCFR_LAUNCH_LDS(shadow_fwd_quad_lds_kernel, true, DEPTH, FUSE, kSchedGrid);
-            } else {
-                if (want_argmin)
-                    GCFR_LAUNCH_LDS(shadow_fwd_quad_argmin_lds_kernel, false, DEPTH, FUSE, kSchedGrid);
-                else
-                    GCFR_LAUNCH_LDS(shadow_fwd_quad_lds_kernel, false, DEPTH, FUSE, kSchedGrid);
-            }
-        }
     } else if (sch == kGridOwn) {  // (argmin wanted: checked by the caller)
         if (even_half)
             GCFR_LAUNCH(shadow_fwd_quad_argmin_own_kernel, true, DEPTH, FUSE, kSchedGrid);
         else
             GCFR_LAUNCH(shadow_fwd_quad_argmin_own_kernel, false, DEPTH, FUSE, kSchedGrid);
     } else {
-        GCFR_LAUNCH_SCHED(kSchedGrid);
+        if (even_half) {
+            if (want_argmin)
+                GCFR_LAUNCH(shadow_fwd_quad_argmin_kernel, true, DEPTH, FUSE, kSchedGrid);
+            else
+                GCFR_LAUNCH(shadow_fwd_quad_kernel, true, DEPTH, FUSE, kSchedGrid);
+        } else {
+            if (want_argmin)
+                GCFR_LAUNCH(shadow_fwd_quad_argmin_kernel, false, DEPTH, FUSE, kSchedGrid);
+            else
+                GCFR_LAUNCH(shadow_fwd_quad_kernel, false, DEPTH, FUSE, kSchedGrid);
+        }
     }
-#undef GCFR_LAUNCH_SCHED
-#undef GCFR_LAUNCH_LDS
 #undef GCFR_LAUNCH
 }
 
 template <int TILE_W, int DEPTH>
-static void launch_quad3(const ShadowQuadArgs &a, bool even_half, bool want_argmin, Schedule sch, dim3 grid,
-                         hipStream_t st, unsigned lds_bytes)
+static void launch_quad3(const ShadowQuadArgs &a, bool even_half, bool want_argmin, Schedule sch, dim3 grid, hipStream_t st)
 {
     if (a.epi.rendered)
-        launch_quad4<TILE_W, DEPTH, true>(a, even_half, want_argmin, sch, grid, st, lds_bytes);
+        launch_quad4<TILE_W, DEPTH, true>(a, even_half, want_argmin, sch, grid, st);
     else
-        launch_quad4<TILE_W, DEPTH, false>(a, even_half, want_argmin, sch, grid, st, lds_bytes);
+        launch_quad4<TILE_W, DEPTH, false>(a, even_half, want_argmin, sch, grid, st);
 }
 
 // The translation units.  launch_march_<tile width>_<group>() is launch_quad3<tile width, group>; each is defined by one
 // compilation of gcfr_march_unit.hip (build.py: MARCH_UNITS) and holds the kernels of that shape.
-typedef void (*MarchUnitFn)(const ShadowQuadArgs &a, bool even_half, bool want_argmin, Schedule sch, dim3 grid,
-                            hipStream_t st, unsigned lds_bytes);
+typedef void (*MarchUnitFn)(const ShadowQuadArgs &a, bool even_half, bool want_argmin, Schedule sch, dim3 grid, hipStream_t st);
 #define GCFR_MARCH_UNIT_NAME_(TW, G) launch_march_##TW##_##G
 #define GCFR_MARCH_UNIT_NAME(TW, G) GCFR_MARCH_UNIT_NAME_(TW, G)
 #define GCFR_DECLARE_MARCH_UNIT(TW, G)                                                                              \
     void GCFR_MARCH_UNIT_NAME(TW, G)(const ShadowQuadArgs &a, bool even_half, bool want_argmin, Schedule sch, dim3 grid, \
-                                     hipStream_t st, unsigned lds_bytes);
+                                     hipStream_t st);
 GCFR_DECLARE_MARCH_UNIT(16, 4)
 #ifndef GCFR_FAST_BUILD   // (development builds have the default shape only: tools/build_variant.sh ... -DGCFR_FAST_BUILD)
 GCFR_DECLARE_MARCH_UNIT(16, 2)

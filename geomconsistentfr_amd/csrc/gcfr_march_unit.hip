@@ -10,9 +10,9 @@
 namespace gcfr {
 
 void GCFR_MARCH_UNIT_NAME(GCFR_UNIT_TILE_W, GCFR_UNIT_GROUP)(const ShadowQuadArgs &a, bool even_half, bool want_argmin,
-                                                             Schedule sch, dim3 grid, hipStream_t st, unsigned lds_bytes)
+                                                             Schedule sch, dim3 grid, hipStream_t st)
 {
-    launch_quad3<GCFR_UNIT_TILE_W, GCFR_UNIT_GROUP>(a, even_half, want_argmin, sch, grid, st, lds_bytes);
+    launch_quad3<GCFR_UNIT_TILE_W, GCFR_UNIT_GROUP>(a, even_half, want_argmin, sch, grid, st);
 }
 
 }  // namespace gcfr

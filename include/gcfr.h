@@ -50,6 +50,9 @@ const char *gcfr_version(void);
  *   6: round 6 -- gcfr_options lost the dead `schedule` / `tile_order` fields (sizeof 64 -> 56: `phase` had gone into what
  *      was tail padding, so revision 5's struct_size could not tell a revision-4 caller from a revision-5 one -- this one
  *      can); gcfr_inference_images_u8 gained `L` (relit images per photograph: many lights per face).
+ *      Still 6: gcfr_options.lds_stage is accepted for compatibility and ignored -- the LDS-staged march it selected (built,
+ *      bit-identical, not faster: profiles/r03_lds_stage_ab.md) builds from commit 0b22e41; gcfr_shadow_workspace_bytes()
+ *      returns what it did (that variant's region is an unused tail now).
  * struct_size guards the struct's SIZE only: a field added into padding does not change it.  The revision check is
  * therefore mandatory for every binding, and every entry point validates struct_size before it reads any other field.
  */
@@ -68,10 +71,8 @@ typedef struct gcfr_options {
     int32_t group;             /* samples per skip group: 1, 2 or 4; 0 = auto (4) */
     int32_t ksplit;            /* split each tile's sample range over the 4 waves of a workgroup: 0, 1, -1 = auto by launch size */
     int32_t depth_bound_skip;  /* exact depth-bound group skip: 0, 1, -1 = auto (on) */
-    int32_t lds_stage;         /* the march's workgroups copy their image's mask (as a bitmap) and depth-bounds records into
-                                  LDS and read them there instead of gathering them through the texture path: 0 off, 1 on
-                                  (wherever the shape allows: W % 32 == 0, 26 KiB per workgroup, default tile and group),
-                                  -1 = auto */
+    int32_t lds_stage;         /* selects nothing: accepted for compatibility (-1, 0 or 1; anything else is rejected) and
+                                  ignored.  It chose the LDS-staged march, which was removed (see the revision history) */
     void *event_start;         /* hipEvent_t recorded on `stream` immediately before the march kernel, or NULL */
     void *event_stop;          /* hipEvent_t recorded immediately after it, or NULL */
     uint64_t *counters;        /* DEVICE array of GCFR_N_COUNTERS + 4 * (number of tiles) u64: the march kernel adds its work

@@ -117,14 +117,14 @@ int main()
         return 1;
     }
     // (1) one call
-    // per-call options: explicit knobs (LDS staging of the mask / bounds records; the NULL-options calls
+    // per-call options: an explicit knob (lds_stage: accepted for compatibility, selects nothing; the NULL-options calls
     // below use the defaults) and an event pair the library records around the march kernel
     gcfr_options opt;
     gcfr_options_default(&opt);
     hipEvent_t ev0, ev1;
     CK(hipEventCreate(&ev0));
     CK(hipEventCreate(&ev1));
-    opt.lds_stage = 1;   // (bit-identical by contract: the three-call forward below runs with the defaults and must agree)
+    opt.lds_stage = 1;   // (ignored: the three-call forward below runs with the defaults and must agree)
     opt.event_start = ev0;
     opt.event_stop = ev1;
     GK(gcfr_render_fwd(d_light, 1, 0.0f, 4013.0f, d_depth, d_mask, B, d_normals, d_albedo, d_amb, B, L, H, W, N,

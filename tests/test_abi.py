@@ -39,9 +39,9 @@ def test_invalid_arguments_are_rejected_without_a_gpu():
     L = _lib.load()
     assert L.gcfr_shadow_fwd(None, None, 1, None, 1, 1, 256, 256, 160, None, 0.0, None, None, None, None, 0, None, None) == -1
     # workspace: quad texels + 4 statistics chunks per 256x256 image (box 16 B + depth range 8 B) + depth-bounds records
-    # (round 3: the records' per-image stride is a whole number of 1-KiB pieces -- 1090 -> 1152 records -- and one mask bitmap of
-    #  H*W/8 bytes per image follows, both for the LDS-staged march; behind each image's records 4 x 1024 float4 of horizon
-    #  tables for the trailing loop's termination test)
+    # (round 3: the records' per-image stride is a whole number of 1-KiB pieces -- 1090 -> 1152 records; behind each image's
+    #  records 4 x 1024 float4 of horizon tables for the trailing loop's termination test.  The H*W/8 bytes per image that the
+    #  LDS-staged march kept its mask bits in are still counted -- an unused tail now, see gcfr_shadow_workspace_bytes)
     assert L.gcfr_shadow_workspace_bytes(8, 256, 256) == (8 * 257 * 257 * 16 + 8 * 4 * 16 + 8 * (1152 + 4096) * 16 + 8 * 4 * 8 + 65 * 4 + 12
                                                           + 8 * 4 * 4 + 16 + 8 * 8192 + 16 + 8 * 4 * 16)     # ... + the masks' partial diagonal extents
     assert L.gcfr_light_prep(None, 1, 1, 0.0, 4013.0, None, None, None) == -1
@@ -88,6 +88,8 @@ def test_options_struct_defaults_and_layout():
     ws_args = args[:14] + (dummy, 1 << 30, None)
     assert L.gcfr_shadow_fwd(*ws_args, ctypes.byref(old)) == -1
     assert L.gcfr_shadow_fwd(*args, ctypes.byref(_lib.options(pixels=2))) == -1
+    # lds_stage selects nothing any more (accepted and ignored: tests/test_gpu_parity.py), but its range is still checked
+    assert L.gcfr_shadow_fwd(*args, ctypes.byref(_lib.options(lds_stage=2))) == -1
     # pixels = mask lives in the workspace path's argmin march: refused (not ignored) without a workspace or without argmin
     assert L.gcfr_shadow_fwd(*args, ctypes.byref(_lib.options(pixels=1))) == -1
     # phase (round 5: the prepass as its own enqueue): off by default, range-checked, and the two halves only exist with a workspace

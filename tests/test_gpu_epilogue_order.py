@@ -17,8 +17,7 @@ albedo, ambient and light per face and light -- the combination in which a value
 up on a partial tile; (64, 64) whole tiles in several workgroups.  (6, 10), (6, 18) and (18, 34) have H/2 or W/2 odd:
 the other half-parity instantiation of every kernel.  The schedule is chosen by the launch's tile count (k-split up to
 2048 tiles: every one of these shapes at every B here), so each case runs as the library picks it AND with the k-split
-forced off (the grid kernel the bench workload runs) AND forced on AND, where the rows are whole bitmap dwords,
-LDS-staged.
+forced off (the grid kernel the bench workload runs) AND forced on.
 """
 import functools
 import os
@@ -107,10 +106,7 @@ def same_bits(a, b):
 
 def schedules(W):
     from geomconsistentfr_amd import _lib
-    s = [("auto", None), ("grid", _lib.options(ksplit=0)), ("ksplit", _lib.options(ksplit=1))]
-    if W % 32 == 0:
-        s.append(("lds", _lib.options(ksplit=0, lds_stage=1)))
-    return s
+    return [("auto", None), ("grid", _lib.options(ksplit=0)), ("ksplit", _lib.options(ksplit=1))]
 
 
 def fused(H, W, B, L, mask_kind, mode, given, options):
@@ -142,7 +138,7 @@ def test_fused_epilogue_equals_the_three_stage_path_bit_for_bit(H, W, B, L):
             ref = reference(H, W, B, L, mask_kind, mode)
             for given in (True, False):
                 for sname, opt in schedules(W):
-                    if mode == "mask" and sname in ("ksplit", "lds"):
+                    if mode == "mask" and sname == "ksplit":
                         continue      # (pixels = mask lives in the grid schedule's own kernel)
                     got = fused(H, W, B, L, mask_kind, mode, given, opt)
                     compare(got, ref, mode, given, (mask_kind, mode, "given" if given else "from depth", sname))
@@ -204,7 +200,7 @@ def test_outputs_are_written_completely_and_nothing_outside_them(H, W, B, L, mon
         for mode in MODES:
             for given in (True, False):
                 for sname, opt in schedules(W):
-                    if mode == "mask" and sname in ("ksplit", "lds"):
+                    if mode == "mask" and sname == "ksplit":
                         continue
                     keep = []
 
@@ -252,7 +248,7 @@ def test_non_finite_depth_at_the_image_corner_poisons_exactly_its_neighbourhood(
         assert same_bits(ref["surface_normals"][ok], clean["surface_normals"][ok]), mode
         for given in (True, False):
             for sname, opt in schedules(W):
-                if mode == "mask" and sname in ("ksplit", "lds"):
+                if mode == "mask" and sname == "ksplit":
                     continue
                 got = R.render_fwd(bad, mask, light, ambient, ref["surface_normals"] if given else None, albedo, prm,
                                    want_argmin=(mode == "argmin"), camera=None if given else (F, F, W / 2.0, H / 2.0, Z_OFF),

@@ -477,15 +477,14 @@ def test_non_increasing_sample_tables_fall_back_to_the_full_march(t0, dt, N):
 
 
 @pytest.mark.parametrize("Hs,Ws,N,dt", [(64, 96, 40, 0.02), (128, 128, 80, 0.01), (256, 256, 160, 0.005), (96, 64, 33, 0.024)])
-def test_lds_staged_march_is_bit_identical(Hs, Ws, N, dt):
-    """gcfr_options.lds_stage = 1 (round 3): the workgroup's mask -- as a bitmap -- and its depth-bounds records are read
-    from LDS instead of being gathered through the texture path.  Same cells, same records, same arithmetic: min_dist
-    and argmin must equal the global-path kernel's and the C oracle's bits -- smooth / rough / offset / negative surfaces,
-    ellipse, all-ones and random masks, one mask shared by the batch, with and without the depth-bound skip, the
-    inference and the training (argmin) kernels, stand-alone and with the fused shading epilogue."""
+def test_grid_march_is_bit_identical_to_the_oracle(Hs, Ws, N, dt):
+    """The grid kernel (one wave per tile, ksplit = 0) at shapes with whole 32-cell rows, where the LDS-staged march of
+    round 3 used to be selectable (these were its cases; the variant is gone): min_dist and argmin must equal the C
+    oracle's bits -- smooth / rough / offset / negative surfaces, ellipse, all-ones and random masks, one mask shared by
+    the batch, with and without the depth-bound skip, the inference and the training (argmin) kernels.  (The fused
+    shading epilogue's outputs: tests/test_gpu_epilogue_order.py.)"""
     import c_oracle
     from geomconsistentfr_amd import RenderParams, _lib, light_prep, shadow_min_distance
-    from geomconsistentfr_amd.block import render_fwd
     rng = np.random.default_rng(Hs * 7 + Ws)
     r, c = np.mgrid[0:Hs, 0:Ws]
     bump = 0.35 * Hs * np.exp(-(((c - 0.5 * Ws) / (0.25 * Ws)) ** 2 + ((r - 0.5 * Hs) / (0.3 * Hs)) ** 2))
@@ -506,34 +505,46 @@ def test_lds_staged_march_is_bit_identical(Hs, Ws, N, dt):
     for zb in (1, 0):
         for want in (True, False):
             md, am = shadow_min_distance(to_dev(depth), to_dev(mask), pt, prm, want_argmin=want, use_workspace=True,
-                                         options=_lib.options(lds_stage=1, ksplit=0, depth_bound_skip=zb))
+                                         options=_lib.options(ksplit=0, depth_bound_skip=zb))
             assert np.array_equal(md.cpu().numpy(), md_o), (zb, want)
             if want:
                 assert np.array_equal(am.cpu().numpy()[lit], am_o[lit]), zb
-    # one mask for the whole batch (mask_batch = 1): per-image bitmaps collapse to one
+    # one mask for the whole batch (mask_batch = 1)
     md_s, _ = c_oracle.shadow_min_distance(depth, np.repeat(mask[3:4], B, 0), pt_o, tt)
     md, _ = shadow_min_distance(to_dev(depth), to_dev(mask[3:4]), pt, prm, want_argmin=False, use_workspace=True,
-                                options=_lib.options(lds_stage=1, ksplit=0))
+                                options=_lib.options(ksplit=0))
     assert np.array_equal(md.cpu().numpy(), md_s)
-    # fused epilogue: every output of the two variants is the same bits
-    amb = to_dev((0.3 + 0.4 * rng.random((B, 2))).astype(np.float32))
-    nrm = to_dev(rng.standard_normal((B, 3, Hs, Ws)).astype(np.float32))
-    alb = to_dev(rng.random((B, 3, Hs, Ws)).astype(np.float32))
-    outs = [render_fwd(to_dev(depth), to_dev(mask), to_dev(lights), amb, nrm, alb, prm, want_argmin=True,
-                       options=_lib.options(lds_stage=ls, ksplit=0)) for ls in (0, 1)]
-    for k in outs[0]:
-        if outs[0][k] is not None:
-            assert torch.equal(outs[0][k], outs[1][k]), k
 
 
-@pytest.mark.parametrize("lds", [0, 1])
-def test_non_finite_inputs_never_make_the_skipping_kernels_differ_from_the_plain_one(lds):
+def test_lds_stage_option_is_accepted_and_ignored():
+    """gcfr_options.lds_stage selected the LDS-staged march until that variant was removed; the field keeps its place in the
+    struct and its range check (tests/test_abi.py), and selects nothing.  At the smallest shape at which the variant used to
+    be chosen (W % 32 == 0, under 26 KiB of LDS): lds_stage = 1 gives the bits of the same call without it."""
+    from geomconsistentfr_amd import RenderParams, _lib, light_prep, shadow_min_distance
+    Hs, Ws, N = 64, 96, 40
+    rng = np.random.default_rng(Hs * 7 + Ws)
+    r, c = np.mgrid[0:Hs, 0:Ws]
+    bump = 0.35 * Hs * np.exp(-(((c - 0.5 * Ws) / (0.25 * Ws)) ** 2 + ((r - 0.5 * Hs) / (0.3 * Hs)) ** 2))
+    depth = np.stack([bump + 3 * rng.random((Hs, Ws)), 30 * rng.random((Hs, Ws))]).astype(np.float32)
+    ell = ((((c - 0.5 * Ws) / (0.4 * Ws)) ** 2 + ((r - 0.5 * Hs) / (0.45 * Hs)) ** 2) < 1)
+    mask = np.stack([ell, rng.random((Hs, Ws)) > 0.2]).astype(np.uint8)
+    lights = np.array([[[0.75, 0.0, 0.66], [0.1, -0.2, 0.97]], [[-0.5, 0.47, 0.72], [0.99, 0.05, 0.05]]], np.float32)
+    prm = RenderParams(n_samples=N, t0=0.025, dt=0.02)
+    _, pt = light_prep(to_dev(lights), prm)
+    md0, am0 = shadow_min_distance(to_dev(depth), to_dev(mask), pt, prm, use_workspace=True, options=_lib.options(ksplit=0))
+    md1, am1 = shadow_min_distance(to_dev(depth), to_dev(mask), pt, prm, use_workspace=True,
+                                   options=_lib.options(lds_stage=1, ksplit=0))
+    assert torch.equal(md0, md1) and torch.equal(am0, am1)
+    assert np.isfinite(md0.cpu().numpy()).all() and (am0.cpu().numpy() >= 0).any()      # (something was marched)
+
+
+def test_non_finite_inputs_never_make_the_skipping_kernels_differ_from_the_plain_one():
     """Round-2 advisor note: with a checked sample table the depth-bounds record offset is used unchecked (`zb_trusted`);
     a raw buffer load answers an out-of-range offset with zeros -- the record "surface is exactly z = 0", a wrong skip --
     so exactness rests on every rounded cell lying inside the image.  It does whatever the inputs: samples sit on the
     segment pixel -> clamped end point, and a non-finite end point (NaN / inf light, `finite_ray` false) collapses the
     segment onto the pixel itself.  Adversarial inputs -- NaN / +-inf depth cells, NaN and inf light components, a
-    light exactly above the image centre -- through the workspace kernels (bounds on and off, global and LDS-staged)
+    light exactly above the image centre -- through the workspace kernels (bounds on and off)
     against the plain direct-gather kernel, which has no bounds machinery: identical bits, NaNs in the same places."""
     from geomconsistentfr_amd import RenderParams, _lib, shadow_min_distance
     rng = np.random.default_rng(77)
@@ -553,12 +564,12 @@ def test_non_finite_inputs_never_make_the_skipping_kernels_differ_from_the_plain
     ref_md, ref_am = shadow_min_distance(to_dev(depth), to_dev(mask), to_dev(pt), prm, use_workspace=False)
     for zb in (1, 0):
         md, am = shadow_min_distance(to_dev(depth), to_dev(mask), to_dev(pt), prm, use_workspace=True,
-                                     options=_lib.options(ksplit=0, depth_bound_skip=zb, lds_stage=lds))
+                                     options=_lib.options(ksplit=0, depth_bound_skip=zb))
         a, b = md.cpu().numpy(), ref_md.cpu().numpy()
         np.testing.assert_array_equal(np.isnan(a), np.isnan(b))
         ok = ~np.isnan(b)
-        assert np.array_equal(a[ok], b[ok]), (zb, lds)
-        assert np.array_equal(am.cpu().numpy()[ok], ref_am.cpu().numpy()[ok]), (zb, lds)
+        assert np.array_equal(a[ok], b[ok]), zb
+        assert np.array_equal(am.cpu().numpy()[ok], ref_am.cpu().numpy()[ok]), zb
     assert np.isnan(ref_md.cpu().numpy()[3]).all() and np.isfinite(ref_md.cpu().numpy()[0]).all()
 
 

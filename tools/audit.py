@@ -143,7 +143,7 @@ def main():
                     help="families that get more seeds: the ones on which the single terms of Kerr are needed for a claim to hold "
                          "(mutant 5, the plane term: steep planar facets under level light; mutant 3, K1: plateaus with pits under an overhead light)")
     ap.add_argument("--config5", type=int, default=0, help="N random faces at configs[4]'s shape (512 x 512 x 320, 18 lights)")
-    ap.add_argument("--tune", type=str, default="", help="gcfr_options knobs, e.g. tile_w=8,group=2 or lds_stage=1 (needs an audit build "
+    ap.add_argument("--tune", type=str, default="", help="gcfr_options knobs, e.g. tile_w=8,group=2 or ksplit=1 (needs an audit build "
                                                           "of every march unit: without -DGCFR_FAST_BUILD)")
     ap.add_argument("--out", type=str, default="")
     a = ap.parse_args()

@@ -178,10 +178,10 @@ def tile_instantiations(tree):
 
 
 def describe_instantiation(name):
-    """march_tile<TILE_W, EVEN_HALF, WANT_ARGMIN, DEPTH, FUSE_SHADE, SPLIT, ALL_ONES, LDS, OWN, MODE>"""
+    """march_tile<TILE_W, EVEN_HALF, WANT_ARGMIN, DEPTH, FUSE_SHADE, SPLIT, ALL_ONES, OWN, MODE>"""
     a = [x.strip() for x in name[name.index("<") + 1:name.rindex(">")].split(",")]
-    mode = {"0": "inline", "1": "bounds variant", "2": "rough variant"}.get(a[9], a[9])
-    return ("all-ones mask" if a[6] == "true" else "mask with zeros") + ", " + mode + (", pixels = mask" if a[8] == "true" else "")
+    mode = {"0": "inline", "1": "bounds variant", "2": "rough variant"}.get(a[8], a[8])
+    return ("all-ones mask" if a[6] == "true" else "mask with zeros") + ", " + mode + (", pixels = mask" if a[7] == "true" else "")
 
 
 def main():

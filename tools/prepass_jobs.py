@@ -14,8 +14,8 @@
 status, a time-out or no result line): what has faulted the device once is not given the next library to fault it again.  Its exit
 status is then 1 and the JSON names the failure.
 
-build_quad_kernel's grid is [horizon tables | depth-bounds tiles | statistics chunks | (bitmap) | repack]; -DGCFR_PREPASS_JOBS leaves the
-grid as it is and makes the blocks of the jobs whose bit is clear return at once (1 horizon, 2 bounds, 4 statistics, 8 bitmap, 16 repack),
+build_quad_kernel's grid is [horizon tables | depth-bounds tiles | statistics chunks | repack]; -DGCFR_PREPASS_JOBS leaves the
+grid as it is and makes the blocks of the jobs whose bit is clear return at once (1 horizon, 2 bounds, 4 statistics, 8 unused, 16 repack),
 so a single job's time includes the dispatch of the other jobs' empty blocks -- which is what it would cost next to faster neighbours.
 The workspace such a library leaves is garbage: only the prepass is timed."""
 import json

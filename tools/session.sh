@@ -17,10 +17,10 @@
 #                    `python tools/summarize_profile.py <tag>` again at home on the merged directories, then tools/design_table.py --write
 #   train_breakdown  rocprofv3 --kernel-trace of tools/train_breakdown.py run     -> train_trace/, train_phases.json, train_step_breakdown.md
 #   audit            tools/audit.py on lib/audit.so (random 800 + every directed family)  -> audit_product.json
-#   audit_matrix     the audit over every tile shape / group size / LDS / k-split (lib/audit_full.so: tools/build_variant.sh audit_full
+#   audit_matrix     the audit over every tile shape / group size / k-split (lib/audit_full.so: tools/build_variant.sh audit_full
 #                    -DGCFR_COUNTERS -DGCFR_AUDIT)                                  -> audit_matrix/*.json, audit_matrix/TOTAL.json
 #   soak             tools/soak_parity.py 10000 cases with and without argmin; tools/soak_backward.py 4000  -> soak_*.json
-#   soak_matrix      the parity soak over every tile shape / group / LDS / k-split / bounds off / pixels = mask  -> soak_matrix/*.json
+#   soak_matrix      the parity soak over every tile shape / group / k-split / bounds off / pixels = mask  -> soak_matrix/*.json
 #   mutants[:n,n..]  tools/mutants.py run + run-audit (build / build-audit on the CPU first) for all or the named mutants
 #   ab:<cfg>|<cfg>   tools/ab.sh interleaved A/B of knob settings / builds ("lib:x.so" entries), AB_EXTRA / AB_STEPS from the environment
 cd ${GRAFT_REPO_ROOT:-/root/repo}
@@ -64,7 +64,7 @@ for step in "$@"; do
     audit_matrix)
       mkdir -p $O/audit_matrix; s=200; export GCFR_HIP_LIB=$PWD/geomconsistentfr_amd/lib/audit_full.so
       for cfg in "tile_w=8,group=4" "tile_w=8,group=2" "tile_w=8,group=1" "tile_w=16,group=4" "tile_w=16,group=2" "tile_w=16,group=1" "tile_w=32,group=4" \
-                 "tile_w=32,group=2" "tile_w=64,group=4" "tile_w=64,group=1" "lds_stage=1" "ksplit=1"; do
+                 "tile_w=32,group=2" "tile_w=64,group=4" "tile_w=64,group=1" "ksplit=1"; do
         s=$((s+1)); f=$(echo $cfg | tr ',=' '__')
         timeout 600 python tools/audit.py --random 400 --family-seeds 4 --seed $s --tune $cfg --out $O/audit_matrix/$f.json > /dev/null 2> $O/audit_matrix/$f.err
       done; unset GCFR_HIP_LIB
@@ -88,7 +88,7 @@ PY
     soak_matrix)
       mkdir -p $O/soak_matrix; s=100
       for cfg in "tile_w=8,group=4" "tile_w=8,group=2" "tile_w=8,group=1" "tile_w=16,group=4" "tile_w=16,group=2" "tile_w=16,group=1" "tile_w=32,group=4" "tile_w=64,group=4" \
-                 "lds_stage=1,ksplit=0" "ksplit=1" "ksplit=0" "depth_bound_skip=0" "pixels=1,ksplit=0" "tile_w=32,group=2,depth_bound_skip=0"; do
+                 "ksplit=1" "ksplit=0" "depth_bound_skip=0" "pixels=1,ksplit=0" "tile_w=32,group=2,depth_bound_skip=0"; do
         s=$((s+1)); f=$(echo $cfg | tr ',=' '__')
         python tools/soak_parity.py --cases 6400 --seed $s --tune $cfg > $O/soak_matrix/argmin_$f.json 2>/dev/null
         [[ "$cfg" == pixels* ]] || python tools/soak_parity.py --cases 3200 --seed $((s+50)) --tune $cfg --no-argmin > $O/soak_matrix/noargmin_$f.json 2>/dev/null
