@@ -10,5 +10,6 @@ from .lighting import area_light, combine_lights, render_rig_from_depth  # noqa:
 from .lighting import (environment_lights, environment_tables, render_environment_from_depth,  # noqa: F401
                        sphere_directions)
 from .lighting import fit_light_rgb, light_normal_equations  # noqa: F401
+from .lighting import environment_lights_frames, rig_frames_u8  # noqa: F401
 
 __version__ = "0.5.0"   # = the library's (gcfr_version(): "gcfr-hip 0.5.0 gfx950")

@@ -110,9 +110,12 @@ _SIGNATURES = {
                                         _p, _p, _p, _p]),
     "gcfr_light_rig_fwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p]),
     "gcfr_light_rig_bwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
+    "gcfr_light_rig_frames_u8": (_i, [_p, _p, _p, _p, _i, _i, _p, _i, _i, _i, _i, _i, _i, _p, _p]),
     "gcfr_environment_cells": (_i, [_p, _p, _p, _i, _i, _i, _f, _p, _p]),
     "gcfr_environment_fwd": (_i, [_p, _i, _i, _i, _p, _p, _i, _p, _p]),
     "gcfr_environment_bwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _p]),
+    "gcfr_environment_cells_frames": (_i, [_p, _p, _p, _i, _i, _i, _i, _f, _p, _p]),
+    "gcfr_environment_fwd_frames": (_i, [_p, _i, _i, _i, _p, _p, _i, _i, _p, _p]),
     "gcfr_light_fit_workspace_bytes": (ctypes.c_size_t, [_i, _i, _i, _i]),
     "gcfr_light_fit_normal": (_i, [_p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p, _p, _p, _p]),
     "gcfr_light_fit_solve": (_i, [_p, _p, _i, _i, _d, _i, _p, _p, _p]),

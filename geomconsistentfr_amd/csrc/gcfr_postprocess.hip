@@ -21,17 +21,12 @@
 //   cv2.imwrite(float image)  saturate_cast<uchar>(cvRound(v)): round half to even, clip to [0, 255]
 // Channel order: the scripts flip to BGR only because cv2 writes BGR; the bytes produced here are RGB, HWC -- what
 // ends up in the PNG.
+#include "gcfr_composite.hpp"
 #include "gcfr_device.hpp"
 
 #include "../../include/gcfr.h"
 
 namespace gcfr {
-
-__device__ inline uint8_t quantise_u8(double v)
-{
-    const double r = __builtin_rint(v);  // cvRound: round half to even
-    return (uint8_t)(r < 0.0 ? 0.0 : (r > 255.0 ? 255.0 : r));  // NaN -> 0 (saturate_cast of INT_MIN)
-}
 
 struct ImagesArgs {
     const float *input_hwc;   // (B,H,W,3) f32 in [0,1]
@@ -59,15 +54,13 @@ __global__ __launch_bounds__(256) void inference_images_kernel(ImagesArgs a)
     if (p >= P)
         return;
     const uint8_t mk = a.mask[(size_t)(a.mask_batch == 1 ? 0 : b) * P + p];
-    const float mf = (float)mk / 255.0f;                                   // SLT:540 (torch: u8 -> f32, IEEE division)
-    const double m = a.mask_f32 ? (double)mf : (double)mk / 255.0;         // value of mask_3_channels (an f64 array)
+    const float mf = mask_quotient_f32(mk);                                // SLT:540 (torch: u8 -> f32, IEEE division)
+    const double m = mask3_value(mk, mf, a.mask_f32);                      // value of mask_3_channels (an f64 array)
     const size_t hwc = ((size_t)b * P + p) * 3, hwc_l = ((size_t)bl * P + p) * 3;
 #pragma unroll
     for (int ch = 0; ch < 3; ++ch) {
-        // input_image = training_images*255.0; rendered_image = 255.0*rendered*mask; input[mask > 0] = rendered[mask > 0]
-        const double keep = (double)a.input_hwc[hwc + ch] * 255.0;
-        const double paste = (double)(255.0f * a.rendered[((size_t)bl * 3 + ch) * P + p]) * m;
-        a.out_rendered[hwc_l + ch] = quantise_u8(m > 0.0 ? paste : keep);
+        // the paste / keep composite (gcfr_composite.hpp, shared with the rig-frames kernel)
+        a.out_rendered[hwc_l + ch] = composite_u8(a.input_hwc[hwc + ch], a.rendered[((size_t)bl * 3 + ch) * P + p], m);
         if (a.out_albedo && first)   // 255.0*albedo*mask3                                   S8:605
             a.out_albedo[hwc + ch] = quantise_u8((double)(255.0f * a.albedo[((size_t)b * 3 + ch) * P + p]) * m);
         if (a.out_normals && first)  // (255.0*(n + 1.0)/2.0)*mask3, n f64 in the reference  S8:594, 608

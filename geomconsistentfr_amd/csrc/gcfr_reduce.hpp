@@ -1,4 +1,4 @@
-// Device primitives shared by the fused heads (gcfr_losses.hip, gcfr_supervised_losses.hip, gcfr_light_rig.hip) and the metrics
+// Device primitives shared by the fused heads (gcfr_losses.hip, gcfr_supervised_losses.hip, gcfr_light_rig.hip, gcfr_rig_frames.hip) and the metrics
 // of gcfr_dataset.hip: the fixed-order f64 sums and the four-pixels-per-lane access.  (gcfr_backward.hip keeps its own DPP
 // reductions, whose totals live in lane 0 only.)
 #pragma once

@@ -17,8 +17,8 @@ import torch
 
 from . import postprocess as pp
 from ._lib import GcfrError
-from .lighting import (MAX_FIT_LIGHTS, _check_environment, _environment_lights, combine_lights, environment_lights, fit_light_rgb,
-                       sphere_directions)
+from .lighting import (MAX_FIT_LIGHTS, _check_environment, _environment_lights, combine_lights, environment_lights,
+                       environment_lights_frames, fit_light_rgb, rig_frames_u8, sphere_directions)
 from .relightnet import RelightNetLightingTransfer, RelightNetSingleImage
 
 # name -> (x, y, z), test_relight_single_image.py:519-562
@@ -183,6 +183,46 @@ def relight_rig(model, images, mask_u8, lights, light_rgb, ambient: float = 0.5,
                               epoch).cpu().numpy()
 
 
+def _as_light_rgb_frames(light_rgb_frames, device) -> torch.Tensor:
+    """F rigs' colour x weight per light as a contiguous f32 device tensor (1|B,F,L,3); (F,L,3) is the same rigs for all faces"""
+    t = (light_rgb_frames if torch.is_tensor(light_rgb_frames) else torch.as_tensor(np.asarray(light_rgb_frames, np.float32)))
+    t = t.to(device=device, dtype=torch.float32)
+    return (t[None] if t.dim() == 3 else t).contiguous()
+
+
+def _rig_frames(x, out, cm, light_rgb_frames, transfer: bool, fix_border: bool) -> torch.Tensor:
+    """`forward_lights`' tuple -> (B,F,H,W,3) uint8: ONE rig-frames launch on its albedo (out[0]) and final shading (out[8]), and
+    the optional border fix on the (B F,H,W,3) view"""
+    frames = rig_frames_u8(out[8], out[0], x, cm, light_rgb_frames, mask_f32=transfer)
+    if fix_border:
+        B, F, H, W, _ = frames.shape
+        frames = pp.fix_border_artifacts_device(frames.reshape(B * F, H, W, 3), cm).reshape(B, F, H, W, 3)
+    return frames
+
+
+@torch.no_grad()
+def relight_rig_frames_device(model, images, mask_u8, lights, light_rgb_frames, ambient: float = 0.5, focal: float = None,
+                              device="cuda", fix_border: bool = False, composite_mask_u8=None, epoch: int = 200) -> torch.Tensor:
+    """`relight_rig_frames` up to the bytes ON THE DEVICE: (B,F,H,W,3) uint8 tensor, nothing copied back.  `images` / `mask_u8` /
+    `lights` / `light_rgb_frames` may already be device tensors."""
+    x = _as_batch(images).to(device)
+    out, cm, transfer = _lights_pass(model, x, mask_u8, lights, ambient, focal, device, composite_mask_u8, epoch)
+    return _rig_frames(x, out, cm, _as_light_rgb_frames(light_rgb_frames, x.device), transfer, fix_border)
+
+
+@torch.no_grad()
+def relight_rig_frames(model, images, mask_u8, lights, light_rgb_frames, ambient: float = 0.5, focal: float = None, device="cuda",
+                       fix_border: bool = False, composite_mask_u8=None, epoch: int = 200) -> np.ndarray:
+    """An ANIMATED rig: every face of `images` (B,H,W,3) under each of the F rigs `light_rgb_frames` (F,L,3) | (1,F,L,3) | (B,F,L,3)
+    of the fixed `lights` (L,3) | (B,L,3) -- a key fading into a fill, a colour sweep, a captured rig cross-faded into another -- as
+    (B,F,H,W,3) uint8 RGB composites.  ONE network pass (`forward_lights`) and L marches in total, then ONE launch
+    (`lighting.rig_frames_u8`) for all F frames, and one more with `fix_border`.  Frame f equals
+    `relight_rig(model, images, mask_u8, lights, light_rgb_frames[:, f], ...)` byte for byte, given the same network outputs.
+    `model` / `ambient` / `focal` as in `relight_lights`.  One device-to-host copy of B*F*H*W*3 bytes at the end."""
+    return relight_rig_frames_device(model, images, mask_u8, lights, light_rgb_frames, ambient, focal, device, fix_border,
+                                     composite_mask_u8, epoch).cpu().numpy()
+
+
 def _as_environment(env, device) -> torch.Tensor:
     """a lat-long radiance map as a contiguous f32 device tensor (1|B,He,We,3); (He,We,3) is one map shared by all faces"""
     t = (env if torch.is_tensor(env) else torch.as_tensor(np.asarray(env, np.float32))).to(device=device, dtype=torch.float32)
@@ -242,14 +282,17 @@ def relight_environment(model, images, mask_u8, env, n_lights: int = 64, rotatio
 @torch.no_grad()
 def relight_environment_frames(model, images, mask_u8, env, rotations, n_lights: int = 64, min_cos: float = -2.0,
                                min_z: float = 0.2, ambient: float = 0.5, focal: float = None, device="cuda",
-                               fix_border: bool = False, composite_mask_u8=None, epoch: int = 200) -> torch.Tensor:
+                               fix_border: bool = False, composite_mask_u8=None, epoch: int = 200, fused: bool = False) -> torch.Tensor:
     """A turntable: every face of `images` under `env` rotated by each of `rotations` (F,3,3), as a (B,F,H,W,3) uint8 DEVICE
     tensor; frame f equals `relight_environment_device(..., rotation=rotations[f])` byte for byte, given the same network outputs.
     The rig's directions are fixed in the face's frame and a rotation changes `light_rgb` only, so the whole turntable is ONE
     network pass and L marches.  The F rotated direction sets are F small matmuls issued before the frames (the single call's own
     `directions @ rotation`, so that the cell maps cannot differ from its in a last bit).  Per frame four launches -- the cell
     map, the integration, the rig combine, the image kernel -- and a fifth with `fix_border`; one more in total stacks the
-    frames."""
+    frames.
+    `fused=True`: the same bytes from the same pass and the same F matmuls, then one stack, ONE cell-map launch and ONE
+    integration launch for all frames (`lighting.environment_lights_frames`), ONE rig-frames launch (`lighting.rig_frames_u8`),
+    and one more with `fix_border` -- no per-frame launch and no f32 image per frame."""
     x = _as_batch(images).to(device)
     directions = _environment_directions(n_lights, min_z, x.device)
     rots = torch.as_tensor(rotations, dtype=torch.float32).to(x.device)
@@ -258,6 +301,8 @@ def relight_environment_frames(model, images, mask_u8, env, rotations, n_lights:
     env_d = _as_environment(env, x.device)
     _check_environment(env_d, directions, None, None, faces=x.shape[0])               # a malformed map fails before the network pass
     out, cm, transfer = _lights_pass(model, x, mask_u8, directions, ambient, focal, device, composite_mask_u8, epoch)
+    if fused:
+        return _rig_frames(x, out, cm, environment_lights_frames(env_d, directions, rots, min_cos), transfer, fix_border)
     dirs_map = [directions @ rots[f] for f in range(rots.shape[0])]
     frames = [_rig_composites(x, out, cm, _environment_lights(env_d, d, min_cos, None), transfer, fix_border) for d in dirs_map]
     return torch.stack(frames, dim=1)

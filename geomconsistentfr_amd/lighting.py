@@ -22,6 +22,12 @@ texel belongs to the direction nearest to it, a light's rgb is the solid-angle-w
     environment_lights             the stage: map + directions (+ rotation) -> light_rgb, differentiable with respect to the map
     render_environment_from_depth  render_rig_from_depth with light_rgb taken from the stage
 
+Rig frames (csrc/gcfr_rig_frames.hip): F rigs per face -- an animated rig, a turntable of an environment map -- from ONE many-lights
+pass, straight to uint8 frames in one launch.
+
+    rig_frames_u8                  final_shading + albedo + photographs + mask + light_rgb_frames (B|1,F,L,3) -> (B,F,H,W,3) uint8
+    environment_lights_frames      environment_lights for F rotations at once -> light_rgb_frames (E,F,L,3): two launches
+
 Rig capture (csrc/gcfr_light_fit.hip), the inverse of the rig stage: the `light_rgb` under which the per-light shadings come closest
 to a photograph, a weighted least-squares problem per face and channel -- "light this face like that photograph".
 
@@ -306,9 +312,9 @@ class _EnvironmentLightsFunction(torch.autograd.Function):
         return g_env, None, None, None          # (no gradient to the directions: the cell map is piecewise constant in them)
 
 
-def _check_environment(env, directions, rotation, out, faces=None):
+def _check_environment(env, directions, rotation, out, faces=None, frames=None):
     """Every shape, dtype and device BEFORE anything is launched or loaded: a mismatch never reaches the kernels.  `faces`: the
-    batch the maps are for (E must be 1 or that)."""
+    batch the maps are for (E must be 1 or that).  `frames`: `out` is the frames form's, (E,frames,L,3)."""
     named = [("env", env), ("directions", directions)] + ([("rotation", rotation)] if rotation is not None else []) \
         + ([("out", out)] if out is not None else [])
     for n, t in named:
@@ -330,9 +336,10 @@ def _check_environment(env, directions, rotation, out, faces=None):
     if directions.device != env.device:
         raise _lib.GcfrError("environment_lights: env and directions on one device; got %s, %s" % (env.device, directions.device))
     if out is not None:
-        if tuple(out.shape) != (E, directions.shape[0], 3) or out.device != env.device or not out.is_contiguous():
-            raise _lib.GcfrError("out must be a contiguous (%d,%d,3) tensor on %s; got %s on %s"
-                                 % (E, directions.shape[0], env.device, tuple(out.shape), out.device))
+        want = (E, directions.shape[0], 3) if frames is None else (E, frames, directions.shape[0], 3)
+        if tuple(out.shape) != want or out.device != env.device or not out.is_contiguous():
+            raise _lib.GcfrError("out must be a contiguous %s tensor on %s; got %s on %s"
+                                 % (want, env.device, tuple(out.shape), out.device))
         if out.requires_grad:
             raise _lib.GcfrError("out must not require a gradient: it is a buffer the result is written into")
     _lib.require_device(env, directions, out)
@@ -383,6 +390,132 @@ def render_environment_from_depth(depth, albedo, directions, ambient, env, camer
     r = render_rig_from_depth(depth, albedo, light, ambient, light_rgb, camera_matrix, z_offset, mask, params, prepared=prepared)
     r["light_rgb"] = light_rgb
     return r
+
+
+# ------------------------------------------------------------------------------------------------------------------------------
+# rig frames: F rigs per face, one launch, uint8 frames
+# ------------------------------------------------------------------------------------------------------------------------------
+MAX_FRAMES = 4096          # include/gcfr.h: 1 <= F <= 4096
+RIG_FRAMES_TILE = 4        # csrc/gcfr_rig_frames.hip kFrameTile: frames per workgroup; final_shading is read ceil(F / 4) times
+
+
+def _check_rig_frames(final_shading, albedo, images, mask_u8, light_rgb_frames, out):
+    """Every tensor that is passed by pointer -- shape, dtype, device -- BEFORE anything is launched or loaded."""
+    named = [("final_shading", final_shading), ("albedo", albedo), ("images", images), ("mask_u8", mask_u8),
+             ("light_rgb_frames", light_rgb_frames)] + ([("out", out)] if out is not None else [])
+    for n, t in named:
+        if not torch.is_tensor(t):
+            raise _lib.GcfrError("rig_frames_u8: %s must be a tensor, got %s" % (n, type(t).__name__))
+        want = torch.uint8 if n in ("mask_u8", "out") else torch.float32
+        if t.dtype != want:
+            raise _lib.GcfrError("rig_frames_u8: %s must be %s, got %s" % (n, str(want).replace("torch.", ""), t.dtype))
+    if any(t.device != final_shading.device for _, t in named):
+        raise _lib.GcfrError("rig_frames_u8: tensors on one device; got %s" % ", ".join(str(t.device) for _, t in named))
+    if final_shading.dim() != 4:
+        raise _lib.GcfrError("final_shading must be (B,L,H,W) -- the many-lights form, with its light axis; got %s"
+                             % (tuple(final_shading.shape),))
+    B, L, H, W = final_shading.shape
+    if B < 1 or H < 1 or W < 1 or not 1 <= L <= MAX_LIGHTS:
+        raise _lib.GcfrError("final_shading (B,L,H,W) = %s: B, H, W >= 1 and 1 <= L <= %d" % (tuple(final_shading.shape), MAX_LIGHTS))
+    if H * W >= 2 ** 31 or B * ((H * W + 1023) // 1024) >= 2 ** 31:
+        raise _lib.GcfrError("final_shading (B,L,H,W) = %s: H W < 2^31 and B ceil(H W / 1024) < 2^31" % (tuple(final_shading.shape),))
+    if tuple(albedo.shape) != (B, 3, H, W):
+        raise _lib.GcfrError("albedo must be %s for final_shading %s; got %s" % ((B, 3, H, W), tuple(final_shading.shape), tuple(albedo.shape)))
+    if tuple(images.shape) != (B, H, W, 3):
+        raise _lib.GcfrError("images must be %s (the photographs, HWC) for final_shading %s; got %s"
+                             % ((B, H, W, 3), tuple(final_shading.shape), tuple(images.shape)))
+    if tuple(mask_u8.shape) not in ((H, W), (1, H, W), (B, H, W)):
+        raise _lib.GcfrError("mask_u8 must be (%d,%d,%d), (1,%d,%d) or (%d,%d); got %s" % (B, H, W, H, W, H, W, tuple(mask_u8.shape)))
+    r = light_rgb_frames
+    if r.dim() not in (3, 4) or tuple(r.shape[-2:]) != (L, 3) or (r.dim() == 4 and r.shape[0] not in (1, B)):
+        raise _lib.GcfrError("light_rgb_frames must be (F,%d,3), (1,F,%d,3) or (%d,F,%d,3) for final_shading %s; got %s"
+                             % (L, L, B, L, tuple(final_shading.shape), tuple(r.shape)))
+    F = r.shape[-3]
+    if not 1 <= F <= MAX_FRAMES:
+        raise _lib.GcfrError("light_rgb_frames %s: 1 <= F <= %d frames" % (tuple(r.shape), MAX_FRAMES))
+    if out is not None and (tuple(out.shape) != (B, F, H, W, 3) or not out.is_contiguous()):
+        raise _lib.GcfrError("out must be a contiguous (%d,%d,%d,%d,3) uint8 tensor; got %s" % (B, F, H, W, tuple(out.shape)))
+    _lib.require_device(*[t for _, t in named])
+    return B, L, F, H, W
+
+
+def rig_frames_u8(final_shading: torch.Tensor, albedo: torch.Tensor, images: torch.Tensor, mask_u8: torch.Tensor,
+                  light_rgb_frames: torch.Tensor, mask_f32: bool = False, out=None) -> torch.Tensor:
+    """(B,F,H,W,3) uint8 frames (RGB, HWC, on the device): every face of the many-lights `final_shading` (B,L,H,W) and `albedo`
+    (B,3,H,W) under each of the F rigs `light_rgb_frames` -- (F,L,3) or (1,F,L,3), the same rigs for all faces, or (B,F,L,3) --
+    pasted into the photographs `images` (B,H,W,3) f32 through the compositing mask `mask_u8` ((B,H,W), or (1,H,W) / (H,W) shared;
+    uint8 as stored on disk).  ONE launch; frame [b,f] equals, byte for byte, `combine_lights(final_shading, albedo,
+    light_rgb_frames[:,f])` followed by `postprocess.inference_images_device(images, rendered, mask_u8, mask_f32=...)`: the same
+    f32 chain in ascending l and the image kernel's own composite function (include/gcfr.h).  `mask_f32`: the mask's quotient in
+    f32 (the lighting-transfer script), else f64.  Nothing is clamped before the quantisation; a NaN gives byte 0.
+    `out`: a contiguous (B,F,H,W,3) uint8 buffer the frames are written into and which is returned.  NOT DIFFERENTIABLE: inputs are
+    detached.  No host synchronisation; a malformed input (rank, shape, dtype, device, L or F out of range) raises GcfrError before
+    anything is loaded or launched, host tensors too.  There is no CPU path."""
+    B, L, F, H, W = _check_rig_frames(final_shading, albedo, images, mask_u8, light_rgb_frames, out)
+    dev = final_shading.device
+    final, alb, x = final_shading.detach().contiguous(), albedo.detach().contiguous(), images.detach().contiguous()
+    m = mask_u8.contiguous().reshape(-1, H, W)
+    rgb = light_rgb_frames.detach().contiguous().reshape(-1, F, L, 3)
+    frames = torch.empty((B, F, H, W, 3), dtype=torch.uint8, device=dev) if out is None else out
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().gcfr_light_rig_frames_u8(final.data_ptr(), alb.data_ptr(), x.data_ptr(), m.data_ptr(), m.shape[0],
+                                                        int(bool(mask_f32)), rgb.data_ptr(), rgb.shape[0], B, L, F, H, W,
+                                                        frames.data_ptr(), _lib.stream_ptr(dev)), "gcfr_light_rig_frames_u8")
+    return frames
+
+
+def _launch_env_cells_frames(rows, cols, dirs_map, He, We, min_cos, cell):
+    F, L, _ = dirs_map.shape
+    dev = dirs_map.device
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().gcfr_environment_cells_frames(rows.data_ptr(), cols.data_ptr(), dirs_map.data_ptr(), F, He, We, L,
+                                                             float(min_cos), cell.data_ptr(), _lib.stream_ptr(dev)),
+                   "gcfr_environment_cells_frames")
+
+
+def _launch_env_fwd_frames(env, row_w, cell, L, rgb):
+    E, He, We, _ = env.shape
+    dev = env.device
+    with torch.cuda.device(dev):
+        _lib.check(_lib.load().gcfr_environment_fwd_frames(env.data_ptr(), E, He, We, row_w.data_ptr(), cell.data_ptr(), cell.shape[0],
+                                                           L, rgb.data_ptr(), _lib.stream_ptr(dev)), "gcfr_environment_fwd_frames")
+
+
+def _check_rotations(rotations):
+    if not torch.is_tensor(rotations):
+        raise _lib.GcfrError("environment_lights_frames: rotations must be a tensor, got %s" % type(rotations).__name__)
+    if rotations.dtype != torch.float32:
+        raise _lib.GcfrError("environment_lights_frames: rotations must be float32, got %s" % rotations.dtype)
+    if rotations.dim() != 3 or tuple(rotations.shape[1:]) != (3, 3) or not 1 <= rotations.shape[0] <= MAX_FRAMES:
+        raise _lib.GcfrError("rotations must be (F,3,3) with 1 <= F <= %d; got %s" % (MAX_FRAMES, tuple(rotations.shape)))
+
+
+def environment_lights_frames(env: torch.Tensor, directions: torch.Tensor, rotations: torch.Tensor, min_cos: float = -2.0,
+                              out=None) -> torch.Tensor:
+    """`light_rgb_frames` (E,F,L,3) -- what `rig_frames_u8` takes -- of the lat-long radiance map(s) `env` (E,He,We,3) for the rig
+    of `directions` (L,3) under each of the F `rotations` (F,3,3; a device or host tensor): entry [:,f] equals
+    `environment_lights(env, directions, rotation=rotations[f], min_cos=min_cos)` bit for bit.  The F rotated direction sets are
+    that call's own F small products `directions @ rotations[f]`, stacked afterwards (a batched product could round differently
+    and move a cell border); then ONE launch builds the F cell maps and ONE integrates them, both running the single call's
+    device code per frame (include/gcfr.h).  `out`: a contiguous (E,F,L,3) f32 buffer the result is written into and which is
+    returned.  The tables of a map size are uploaded by the first call for that (He, We, device), as in `environment_lights`: make
+    that call outside a stream capture.  NOT DIFFERENTIABLE in this form.  A malformed input raises GcfrError before any launch,
+    host `env` / `directions` too."""
+    _check_rotations(rotations)
+    _check_environment(env, directions, None, out, frames=rotations.shape[0])
+    E, He, We, _ = env.shape
+    L, F = directions.shape[0], rotations.shape[0]
+    if E * F * L >= 2 ** 31:
+        raise _lib.GcfrError("environment_lights_frames: E F L < 2^31 (one workgroup per map, frame and light); got %d x %d x %d" % (E, F, L))
+    dev = env.device
+    d, rots = directions.detach(), rotations.detach().to(dev)
+    dirs_map = torch.stack([d @ rots[f] for f in range(F)])                        # (F,L,3): the single call's products, stacked
+    rows, row_w, cols = _device_tables(He, We, dev)
+    cell = torch.empty((F, He, We), dtype=torch.int32, device=dev)
+    rgb = torch.empty((E, F, L, 3), dtype=torch.float32, device=dev) if out is None else out
+    _launch_env_cells_frames(rows, cols, dirs_map, He, We, min_cos, cell)
+    _launch_env_fwd_frames(env.detach().contiguous(), row_w, cell, L, rgb)
+    return rgb
 
 
 # ------------------------------------------------------------------------------------------------------------------------------

@@ -582,6 +582,36 @@ int gcfr_light_rig_bwd(const float *final_shading, const float *albedo, const fl
                        int32_t H, int32_t W, const float *g_rendered, const float *g_shading_rgb, float *g_final, float *g_albedo,
                        double *g_rgb, void *stream);
 
+/*
+ * Rig frames, one launch (csrc/gcfr_rig_frames.hip): F rigs per face combined with the per-light shadings of ONE many-lights pass
+ * and pasted into the photograph, straight to uint8 frames -- an animated rig or a turntable of an environment map.  It replaces,
+ * per frame, gcfr_light_rig_fwd above followed by gcfr_inference_images_u8 at L = 1 (the scripts' S1:601-620 / SLT:567-572 on
+ * T8:519-522's composite); the f32 `rendered` is not written.  All planes contiguous:
+ *   final_shading (B,L,H,W) f32            the many-lights `final` (T8:518 per light)
+ *   albedo        (B,3,H,W) f32
+ *   input_hwc     (B,H,W,3) f32            the photographs, as gcfr_inference_images_u8 takes them
+ *   mask          (mask_batch,H,W) u8      the compositing mask as stored on disk; mask_batch = B or 1
+ *   mask_f32      0 / 1                    the mask's quotient in f64 (S1:580) or in f32, widened (SLT:540), as gcfr_inference_images_u8
+ *   rgb           (rgb_batch,F,L,3) f32    colour x weight of every light of every frame; rgb_batch = B (rigs per face) or 1
+ *   frames        (B,F,H,W,3) u8 out       RGB, HWC
+ * B >= 1, 1 <= L <= 4096, 1 <= F <= 4096, H, W >= 1 (any parity) with H W < 2^31 and B ceil(H W / 1024) < 2^31; anything else, a
+ * NULL pointer, mask_batch / rgb_batch other than 1 / B or mask_f32 other than 0 / 1 is GCFR_ERR_INVALID_ARGUMENT before the
+ * launch.  Allocates nothing, never synchronises, may be captured into a graph.  No output may alias an input.
+ * Numerical contract: frames[b,f] equals, BYTE FOR BYTE, gcfr_light_rig_fwd with rgb[.,f] followed by gcfr_inference_images_u8 with
+ * L = 1 on its `rendered`, by construction: per pixel and channel the rig stage's chain, every product and sum one IEEE f32
+ * operation -- acc = rgb[f,0,c] final[0]; acc = acc + rgb[f,l,c] final[l] for l = 1 .. L-1 ascending; rendered = albedo[c] acc --
+ * and then the image kernel's own composite (one shared device function, csrc/gcfr_composite.hpp):
+ *   m = mask_f32 ? (double)((float)mk / 255.0f) : (double)mk / 255.0
+ *   byte = saturate(rint(m > 0 ? (double)(255.0f * rendered) * m : (double)input * 255.0))      round half to even; NaN -> 0
+ * Nothing is clamped before the quantisation.  Bit-equal to the composition of the two restatements
+ * (tests/rig_frames_emulation.py).  Planes move in 16-byte accesses and a frame's 12 bytes per four pixels in three dword stores
+ * when H W is a multiple of 4, final_shading / albedo / input_hwc are 16-byte aligned and mask / frames 4-byte aligned; one
+ * element at a time otherwise (same results).  A plane of final_shading is read ceil(F / 4) times, not F times.
+ */
+int gcfr_light_rig_frames_u8(const float *final_shading, const float *albedo, const float *input_hwc, const uint8_t *mask,
+                             int32_t mask_batch, int32_t mask_f32, const float *rgb, int32_t rgb_batch, int32_t B, int32_t L,
+                             int32_t F, int32_t H, int32_t W, uint8_t *frames, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Environment-map lighting: a lat-long radiance map integrated into the `rgb` (colour x weight per light) of the light-rig stage
  * above (csrc/gcfr_environment.hip).  Every texel belongs to the light direction nearest to it; a light's rgb is the
@@ -630,6 +660,19 @@ int gcfr_environment_fwd(const float *env, int32_t E, int32_t He, int32_t We, co
  */
 int gcfr_environment_bwd(const float *g_rgb, const double *row_w, const int32_t *cell, int32_t E, int32_t He, int32_t We, int32_t L,
                          float *g_env, void *stream);
+
+/*
+ * The two forward stages with a FRAME axis, one launch each (a turntable: F rotations of the rig's directions against one map).
+ *   dirs_map (F,L,3) f32   ->   cell_out (F,He,We) i32             gcfr_environment_cells_frames
+ *   cell (F,He,We) i32, env (E,He,We,3) f32   ->   rgb_out (E,F,L,3) f32, the layout gcfr_light_rig_frames_u8 takes
+ * 1 <= F <= 4096 and L E F < 2^31 besides the ranges above.  Frame f is gcfr_environment_cells / gcfr_environment_fwd on
+ * dirs_map[f] / cell[f] BIT FOR BIT: the kernels call the same device functions for the per-texel score loop and for the lane walk
+ * and its fixed-order f64 sum; only the frame's offset into dirs_map, cell and rgb_out is added.  No backward in this form.
+ */
+int gcfr_environment_cells_frames(const float *rows, const float *cols, const float *dirs_map, int32_t F, int32_t He, int32_t We,
+                                  int32_t L, float min_cos, int32_t *cell_out, void *stream);
+int gcfr_environment_fwd_frames(const float *env, int32_t E, int32_t He, int32_t We, const double *row_w, const int32_t *cell,
+                                int32_t F, int32_t L, float *rgb_out, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Rig capture: the `rgb` (colour x weight per light) of the light-rig stage above FITTED to a photograph, by weighted least squares
