@@ -6,6 +6,9 @@ Device path (HIP kernels of csrc/gcfr_postprocess.hip, no CPU fallback): `infere
   inference_images_device       S1:614-620 / S8:583-608 / SLT:547-579: composite + the five diagnostic maps, quantised
                                 to the bytes cv2.imwrite stores
   fix_border_artifacts_device   fix_border_artifacts_CVPR2022.m:1-18
+  ingest_photographs_device     the uint8 photograph at 1, 2, 4 or 8 times the network's side -> the network's f32 input
+                                (S1:515/580 without the host-side cv2.resize), csrc/gcfr_fullres.hip
+  fullres_composites_device     the relit low-resolution images carried back onto the photograph's own pixels, uint8
 
 Host side: the on-disk formats of load_data() (T8:545-556).  The numpy statements of the script lines these kernels
 implement live in oracle/postprocess_statements.py (test infrastructure, pinned to the reference's own main() by
@@ -87,6 +90,95 @@ def fix_border_artifacts_device(img_u8, face_mask_u8):
         _lib.check(_lib.load().gcfr_fix_border_u8(img.data_ptr(), mk.data_ptr(), mk.shape[0], B, H, W, out.data_ptr(),
                                                   torch.cuda.current_stream(img.device).cuda_stream), "gcfr_fix_border_u8")
     return out
+
+
+FULLRES_SCALES = (1, 2, 4, 8)       # photograph side / network side (csrc/gcfr_fullres.hip)
+FULLRES_MAX_LIGHTS = 4096
+
+
+def _check_photographs(photo_u8, scale, what):
+    """-> (B, h, w, s) of uint8 photographs (B, s h, s w, 3) on the device, or GcfrError"""
+    import torch
+    from . import _lib
+    if not torch.is_tensor(photo_u8) or photo_u8.dtype != torch.uint8 or photo_u8.dim() != 4 or photo_u8.shape[-1] != 3:
+        raise _lib.GcfrError("%s: photographs must be a uint8 tensor (B,H,W,3); got %s" % (
+            what, (tuple(photo_u8.shape), photo_u8.dtype) if torch.is_tensor(photo_u8) else type(photo_u8).__name__))
+    if isinstance(scale, bool) or not isinstance(scale, int) or scale not in FULLRES_SCALES:
+        raise _lib.GcfrError("%s: scale must be one of %s; got %r" % (what, FULLRES_SCALES, scale))
+    B, H, W, _ = photo_u8.shape
+    if B < 1 or H < 1 or W < 1 or H % scale or W % scale:
+        raise _lib.GcfrError("%s: photographs %s are not (B, scale h, scale w, 3) for scale %d" % (what, tuple(photo_u8.shape), scale))
+    if H * W > 0x7fffffff or B * ((H * W + 1023) // 1024) > 0x7fffffff:
+        raise _lib.GcfrError("%s: %d photographs of %d x %d pixels do not fit the kernels' 31-bit pixel and chunk counts" % (what, B, H, W))
+    _lib.require_device(photo_u8)
+    return B, H // scale, W // scale, scale
+
+
+def ingest_photographs_device(photo_u8, scale):
+    """The network's input from the photographs, on the device: photo_u8 (B, s h, s w, 3) uint8 -> (B,h,w,3) f32 in [0,1], the
+    mean of every s x s block of bytes over 255 (the integer sum, one f64 division, one rounding to f32: csrc/gcfr_fullres.hip).
+    `scale` s is 1, 2, 4 or 8; at 1 the result has the bits of np.float32(img / 255.0), what the scripts feed the network
+    (S1:515/580).  Replaces the scripts' host-side cv2.resize and the upload of an f32 image.  One launch, no host
+    synchronisation; a malformed input raises GcfrError before anything is loaded or launched."""
+    import torch
+    from . import _lib
+    B, h, w, s = _check_photographs(photo_u8, scale, "ingest_photographs_device")
+    photo = photo_u8.detach().contiguous()
+    x_lo = torch.empty((B, h, w, 3), dtype=torch.float32, device=photo.device)
+    with torch.cuda.device(photo.device):
+        _lib.check(_lib.load().gcfr_ingest_photographs_u8(photo.data_ptr(), B, h, w, s, x_lo.data_ptr(), _lib.stream_ptr(photo.device)),
+                   "gcfr_ingest_photographs_u8")
+    return x_lo
+
+
+def fullres_composites_device(photo_u8, x_lo, rendered, mask_u8, scale, detail_clamp=4.0, floor=1.0, out=None):
+    """The relit low-resolution `rendered` of ONE pass carried back onto the photographs' own pixels, as uint8 on the device:
+    photo_u8 (B, s h, s w, 3) uint8; x_lo (B,h,w,3) f32, the network's input (`ingest_photographs_device`); rendered (B,L,3,h,w)
+    -> (B,L,H,W,3), or (B,3,h,w) -> (B,H,W,3); mask_u8 (1|B,h,w) or (h,w) uint8, the compositing mask AT THE NETWORK'S RESOLUTION
+    as stored on disk.  Quotient / detail transfer (include/gcfr.h states every operation): the photograph's detail relative to
+    its own low-resolution version, d = clamp(photo / max(255 Up(x_lo), floor), 1 / detail_clamp, detail_clamp), multiplies the
+    bilinearly upsampled relit image, and the upsampled mask m BLENDS it with the photograph, v = p + m (255 Up(rendered) d - p);
+    where m is 0 the photograph's byte is kept, whatever `rendered` holds there.  `floor` is in grey levels.  ONE launch for all L
+    lights: the photograph, x_lo and the mask are read once per pixel.  `rendered` is the only operand that may be non-f32 on
+    entry.  `out`: a contiguous uint8 buffer of the result's shape that is written and returned (not the photographs).  NOT
+    DIFFERENTIABLE.  No host synchronisation; a malformed input raises GcfrError before anything is loaded or launched."""
+    import torch
+    from . import _lib
+    what = "fullres_composites_device"
+    B, h, w, s = _check_photographs(photo_u8, scale, what)
+    H, W = s * h, s * w
+    if not torch.is_tensor(x_lo) or x_lo.dtype != torch.float32 or tuple(x_lo.shape) != (B, h, w, 3):
+        raise _lib.GcfrError("%s: x_lo must be a float32 tensor (%d,%d,%d,3); got %s" % (
+            what, B, h, w, (tuple(x_lo.shape), x_lo.dtype) if torch.is_tensor(x_lo) else type(x_lo).__name__))
+    if not torch.is_tensor(rendered) or not rendered.is_floating_point() or rendered.dim() not in (4, 5):
+        raise _lib.GcfrError("%s: rendered must be a floating-point tensor (B,3,h,w) or (B,L,3,h,w)" % what)
+    multi = rendered.dim() == 5
+    L = rendered.shape[1] if multi else 1
+    lead = (B, L) if multi else (B,)
+    if tuple(rendered.shape) != lead + (3, h, w) or not 1 <= L <= FULLRES_MAX_LIGHTS:
+        raise _lib.GcfrError("%s: rendered must be (%d,3,%d,%d) or (%d,L,3,%d,%d) with 1 <= L <= %d; got %s" % (
+            what, B, h, w, B, h, w, FULLRES_MAX_LIGHTS, tuple(rendered.shape)))
+    if not torch.is_tensor(mask_u8) or mask_u8.dtype != torch.uint8:
+        raise _lib.GcfrError("%s: mask_u8 must be the uint8 skin mask (0..255) at the network's resolution" % what)
+    if tuple(mask_u8.shape) not in ((h, w), (1, h, w), (B, h, w)):
+        raise _lib.GcfrError("%s: mask_u8 must be (%d,%d), (1,%d,%d) or (%d,%d,%d); got %s" % (what, h, w, h, w, B, h, w, tuple(mask_u8.shape)))
+    if not float(detail_clamp) >= 1.0 or not float(floor) > 0.0:
+        raise _lib.GcfrError("%s: detail_clamp >= 1 and floor > 0; got %r, %r" % (what, detail_clamp, floor))
+    if out is not None:
+        if not torch.is_tensor(out) or out.dtype != torch.uint8 or tuple(out.shape) != lead + (H, W, 3) or not out.is_contiguous():
+            raise _lib.GcfrError("%s: out must be a contiguous uint8 tensor %s" % (what, lead + (H, W, 3)))
+    _lib.require_device(x_lo, rendered, mask_u8, out)
+    photo, x = photo_u8.detach().contiguous(), x_lo.detach().contiguous()
+    ren = rendered.detach().to(torch.float32).contiguous()
+    m = mask_u8.contiguous().reshape(-1, h, w)
+    if out is not None and out.data_ptr() == photo.data_ptr():
+        raise _lib.GcfrError("%s: out must not be the photographs" % what)
+    res = torch.empty(lead + (H, W, 3), dtype=torch.uint8, device=photo.device) if out is None else out
+    with torch.cuda.device(photo.device):
+        _lib.check(_lib.load().gcfr_fullres_composites_u8(photo.data_ptr(), x.data_ptr(), ren.data_ptr(), m.data_ptr(), m.shape[0], B, L,
+                                                          h, w, s, float(floor), float(detail_clamp), res.data_ptr(),
+                                                          _lib.stream_ptr(photo.device)), "gcfr_fullres_composites_u8")
+    return res
 
 
 # ------------------------------------------------------------------------------------------------

@@ -613,6 +613,42 @@ int gcfr_light_rig_frames_u8(const float *final_shading, const float *albedo, co
                              int32_t F, int32_t H, int32_t W, uint8_t *frames, void *stream);
 
 /* ---------------------------------------------------------------------------------------------
+ * Full-resolution relighting (csrc/gcfr_fullres.hip): the two ends of the inference path around the network's resolution (h, w).
+ * The photograph is (s h, s w) with s = 1, 2, 4 or 8 (H = s h, W = s w; every bilinear weight is then a multiple of 1 / (2 s),
+ * exact in f32).  All arrays contiguous:
+ *   photo_u8   (B,H,W,3) u8                 the photographs, RGB, HWC
+ *   x_lo       (B,h,w,3) f32                the network's input: what gcfr_ingest_photographs_u8 writes
+ *   rendered   (B,L,3,h,w) f32              the relit images of ONE many-lights pass
+ *   mask_u8    (mask_batch,h,w) u8          the compositing mask AT THE NETWORK'S RESOLUTION, as stored on disk; mask_batch = B or 1
+ *   out_u8     (B,L,H,W,3) u8 out
+ * Every operation is one separately rounded IEEE f32 operation unless marked f64; max / min are fmaxf / fminf.
+ *   Ingest:  x_lo[b,i,j,c] = (float)((double)S / (255.0 s s)), S the integer sum of the s x s block of bytes; at s = 1 the bits of
+ *            np.float32(img / 255.0) (S1:515/580).
+ *   Up(a), bilinear with half-pixel centres, per axis and hi-res index y: fy = max((y + 0.5) / s - 0.5, 0), y0 = floor(fy),
+ *            t = fy - y0, y1 = min(y0 + 1, n - 1) (all exact); horizontal first on both rows as a0 + tx (a1 - a0), then
+ *            top + ty (bot - top).  A constant field is returned exactly.  Both taps are always read (a tap of weight 0 still
+ *            carries a NaN into its pixel).
+ *   Composite, per hi-res pixel, light l and channel c:
+ *            p = (float)photo_u8;  xl = Up(x_lo[..., c]) 255.0f;  d = min(max(p / max(xl, floor), 1.0f / detail_clamp), detail_clamp)
+ *            m = Up((float)mask_u8 / 255.0f);  r = Up(rendered[b,l,c]) 255.0f;  v = p + m (r d - p)
+ *            byte = m > 0 ? saturate(rint((double)v)) : photo_u8       the image kernel's quantisation (round half to even, NaN -> 0)
+ *   `floor` (in grey levels) keeps the quotient finite in the dark; `detail_clamp` bounds it to [1 / detail_clamp, detail_clamp].
+ *   Outside the mask (m = 0) the photograph's byte is copied: nothing in `rendered` can reach it.  The mask BLENDS here (the
+ *   low-resolution composite pastes rendered * mask).
+ * B, h, w >= 1 (any parity), 1 <= L <= 4096, H W < 2^31 and B ceil(H W / 1024) < 2^31; anything else, a NULL pointer, s not in
+ * {1,2,4,8}, mask_batch other than 1 / B, out_u8 == photo_u8, detail_clamp < 1 or floor <= 0 (or either a NaN) is
+ * GCFR_ERR_INVALID_ARGUMENT before the launch.  One launch each; allocates nothing, never synchronises, may be captured into a
+ * graph.  No output may alias an input.  Bit-equal to the numpy restatement (tests/fullres_emulation.py).  The composite moves the
+ * photograph's and each light's 12 bytes per four pixels as three dwords when W is a multiple of 4 and photo_u8 / out_u8 are 4-byte
+ * aligned (the ingest: w a multiple of 4, photo_u8 4-byte and x_lo_out 16-byte aligned); one element at a time otherwise (same
+ * results).  The photograph, x_lo and the mask are read once per pixel, not once per light.
+ */
+int gcfr_ingest_photographs_u8(const uint8_t *photo_u8, int32_t B, int32_t h, int32_t w, int32_t s, float *x_lo_out, void *stream);
+int gcfr_fullres_composites_u8(const uint8_t *photo_u8, const float *x_lo, const float *rendered, const uint8_t *mask_u8,
+                               int32_t mask_batch, int32_t B, int32_t L, int32_t h, int32_t w, int32_t s, float floor,
+                               float detail_clamp, uint8_t *out_u8, void *stream);
+
+/* ---------------------------------------------------------------------------------------------
  * Environment-map lighting: a lat-long radiance map integrated into the `rgb` (colour x weight per light) of the light-rig stage
  * above (csrc/gcfr_environment.hip).  Every texel belongs to the light direction nearest to it; a light's rgb is the
  * solid-angle-weighted sum of its texels.  No kernel evaluates a transcendental function: the trigonometry arrives in host-built
