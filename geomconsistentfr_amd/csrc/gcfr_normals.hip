@@ -54,7 +54,9 @@ static int normals_launch(bool backward, const float *depth, const float *grad_n
                           int32_t W, double fx, double fy, double cx, double cy, float z_offset,
                           int32_t negate_y, float *normals, float *grad_depth, void *stream)
 {
-    if (!depth || B <= 0 || H <= 0 || W <= 0 || B > 65535 || fx == 0.0 || fy == 0.0)
+    // H, W >= 2: a one-pixel-wide image has no horizontal (vertical) neighbour at all, which unit_normal_from() does not
+    // evaluate (its "one side always exists") and for which the restated algorithm gives the zero vector, not a unit normal
+    if (!depth || B <= 0 || H < 2 || W < 2 || B > 65535 || fx == 0.0 || fy == 0.0)
         return GCFR_ERR_INVALID_ARGUMENT;
     if (backward ? (!grad_normals || !grad_depth) : !normals)
         return GCFR_ERR_INVALID_ARGUMENT;

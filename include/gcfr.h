@@ -194,6 +194,10 @@ int gcfr_shade_fwd(const float *normals, const float *depth, const float *albedo
  * camera matrix, normalised 3x3 Sobel with replicate padding, cross, normalise) -- parity UNPINNED.
  *   depth (B,H,W) f32;  fx, fy, cx, cy from intrinsic_matrix (T8:571-577);  z_offset added in f32
  *   negate_y: 1 = apply T8:354;  normals (B,3,H,W) f32 out, unit length
+ * 1 <= B <= 65535, H >= 2 and W >= 2 (any parity), fx and fy non-zero; anything else, or a NULL buffer, is
+ * GCFR_ERR_INVALID_ARGUMENT before a launch, for gcfr_normals_fwd and gcfr_normals_bwd alike.  A one-pixel-wide image is refused
+ * because replicate padding then makes both neighbours of a pixel the pixel itself: dP/du (W = 1) or dP/dv (H = 1) is the zero
+ * vector, the cross product vanishes and the restated algorithm returns 0 / 1e-12, not a unit normal.
  * Numerical contract (also of the normals the fused epilogue of gcfr_render_from_depth_fwd computes and of `normals_out`):
  * NOT bit-reproducible against another evaluation order -- the reference's chain is f64 with an unspecified conv2d
  * summation order, and the kernels use reciprocals / v_rsq + Newton steps instead of IEEE divisions -- but within 4 f32
