@@ -510,6 +510,9 @@ enum { kModeInline = 0, kModeFull = 1, kModeRough = 2 };
                                 // then; since round 5's trims 3 and 4 fit the 80 registers: noise-400 faces +2.2 % / +0.7 %, the bench
                                 // faces, the FFHQ fixtures and all-ones masks unchanged, profiles/r05_rough_chunk_ab.txt)
 #endif
+#ifndef GCFR_BODY_PIPELINE
+#define GCFR_BODY_PIPELINE 1    // 0: every kernel keeps the one-at-a-time group body (A/B: tools/build_variant.sh <name> -DGCFR_BODY_PIPELINE=0)
+#endif
 #ifndef GCFR_ROUGH_CHUNK_ARGMIN
 #define GCFR_ROUGH_CHUNK_ARGMIN 3   // ... five-wave training march
 #endif
@@ -544,6 +547,9 @@ __device__ __forceinline__ bool march_tile(ArgPtr a, const int bl, const int qy,
     // the trailing loop, see the sample loop (all-ones masks too: there is no mask work to save, but its termination test is the sharper one)
     constexpr bool TRAIL = !KSPLIT;
     constexpr bool ROUGH = MODE == kModeRough;  // the rough loop, see the sample loops
+    // the group body as a rotating pair of texel gathers with the next group's prefetch behind it (see consume()): the six-wave
+    // fused inference grid kernels
+    constexpr bool PIPE = GCFR_BODY_PIPELINE && !WANT_ARGMIN && !KSPLIT && !ROUGH && FUSE_SHADE && DEPTH >= 2;
     const int chunk = KSPLIT ? (a->N + 3) >> 2 : a->N;
     const int k_lo = KSPLIT ? wave * chunk : 0;
     const int N = KSPLIT ? min(a->N, k_lo + chunk) : a->N;  // exclusive upper bound ("N" below)
@@ -1065,8 +1071,10 @@ __device__ __forceinline__ bool march_tile(ArgPtr a, const int bl, const int qy,
     };
 // census: loop: group bookkeeping (ballots, branches)
     bool all_lazy = false;  // (wave-uniform) set by consume(): the group just consumed could have been skipped without its mask
+    // late(): (PIPE only, see the body) what the caller wants requested once the decision about the body is taken -- the
+    // next group's prefetch in the main loop, nothing in the trailing loop, whose record fetch comes behind consume() anyway.
     auto consume = [&](int k0, const uint32_t (&cm)[DEPTH], const f32x4 &cz, double ta64, double tb64, double tn64,
-                       bool check_finished, auto lazy, bool cw_in) -> bool {
+                       bool check_finished, auto lazy, bool cw_in, auto late) -> bool {
         constexpr bool LAZY = decltype(lazy)::value;
         if (TRAIL)
             all_lazy = false;
@@ -1093,7 +1101,8 @@ __device__ __forceinline__ bool march_tile(ArgPtr a, const int bl, const int qy,
                 all_lazy = !run_body && __builtin_amdgcn_ballot_w64(!((cannot_win && GCFR_M(18, true, (bestS < safeS))) || (lane_last < k0))) == 0ull;
         }
         // samples of the group evaluated together (texel gathers in flight): one at a time in the six-wave inference
-        // variant (fewer live registers -> forced occupancy, see the __global__ wrappers), two in the argmin variant, the
+        // variant (fewer live registers -> forced occupancy, see the __global__ wrappers) -- except in the main loop of its fused
+        // kernels, which keeps a rotating pair in flight (PIPE, below) --, two in the argmin variant, the
         // whole group in the k-split variant, whose launches are tiny and latency-bound
         // (the argmin variant runs at five waves per SIMD and has the registers for two gathers in flight: +5 % on smooth and on
         //  rough depth, round 3; the six-wave inference variant at five waves with two in flight: -2 ... -3 %)
@@ -1116,8 +1125,11 @@ __device__ __forceinline__ bool march_tile(ArgPtr a, const int bl, const int qy,
           for (int j = 0; j < DEPTH; ++j)
               cnt[kCntLaneSamples] += (unsigned)__builtin_popcountll(__builtin_amdgcn_ballot_w64(cm[j] != 0));
 #endif
-#pragma unroll
 // census: loop: sample body (bilinear, distance, minimum)
+          // (the plain body comes FIRST in the text: a lambda captures in the order of first use, and with the pair in front the
+          //  kernels that do not take it were allocated other scalar registers -- the same instructions, two SGPR pairs swapped)
+          if (!(PIPE && !LAZY)) {
+#pragma unroll
           for (int h0 = 0; h0 < DEPTH; h0 += GCFR_BODY_CHUNK) {
             // phase 1: positions and texel gathers for the whole group (all in flight together)
             double ux[DEPTH], uy[DEPTH], fxd[DEPTH], fyd[DEPTH];
@@ -1146,6 +1158,53 @@ __device__ __forceinline__ bool march_tile(ArgPtr a, const int bl, const int qy,
             for (int j = h0; j < h0 + GCFR_BODY_CHUNK && j < DEPTH; ++j)
                 eval_sample(clampk(k0 + j), (cm[j] == 0) || dead, ux[j], uy[j], fxd[j], fyd[j], qv[j]);
           }
+          } else {
+            // (The trailing loop's leave path, LAZY, keeps the plain body: with the pair there the six-wave kernel of even W/2 and
+            //  H/2 spills 12 B -- a packed pair of the cross product's constants, stored in front of the trailing loop and
+            //  reloaded in its bodies --, with chunked pairs (0,1 | 2,3) 16 B.  On the bench faces it runs at most 0.37 of a tile's 3.63
+            //  bodies: profiles/r08_work_counts.json, trail_leave.)
+            // Rotating pair: gathers 0 and 1 are issued, 0 is evaluated, 2 issued, 1 evaluated, ... -- behind the first wait every
+            // texel has one whole evaluation (~35 instructions) to come back in, where one at a time exposes each round trip in
+            // full.  A sample in flight holds its texel and (ux, uy): the floors are recomputed where they are consumed, from
+            // LAUNDERED ux / uy (or the optimiser carries the floors of the address computation across the flight), and the
+            // group's masked flags ride in one laundered register, so that the mask bytes are dead across the body.  The caller's
+            // late() -- the next group's prefetch -- is requested behind the issue of the last texel gather: it comes back under
+            // the last evaluations and its destination registers are not live across the body.  Same arithmetic per sample, same
+            // order of samples.
+            uint32_t mflags = 0u;
+#pragma unroll
+            for (int j = 0; j < DEPTH; ++j)
+                mflags |= (cm[j] == 0 ? 1u : 0u) << j;
+            mflags = dead ? ~0u : mflags;
+            asm volatile("" : "+v"(mflags));
+            double ux[DEPTH], uy[DEPTH];
+            f32x4 qv[DEPTH];
+            auto issue = [&](int j) {
+                constexpr bool CARRIED = FUSE_SHADE || WANT_ARGMIN;  // (see the plain body)
+                const double tj = (CARRIED && j == 0) ? ta64 : ((CARRIED && j == DEPTH - 1) ? tb64 : (double)tt[clampk(k0 + j)]);
+                const double sx = x64 + tj * dx64, sy = y64 + tj * dy64;  // T8:472 / 480 (mul and add rounded separately)
+                ux[j] = (sx + halfW) - 0.0001;  // unrounded position (T8:480-487)
+                uy[j] = (halfH - sy) - 0.0001;
+                const int fx = (int)__builtin_floor(ux[j]), fy = (int)__builtin_floor(uy[j]);  // may be -1: the quad grid has that row / column
+                const int texel = __mul24(fy, Wp) + fx;
+                qv[j] = __builtin_bit_cast(
+                    f32x4, __builtin_amdgcn_raw_buffer_load_b128(qr, (texel << 4) + quad_origin, 0, 0));
+                asm volatile("" : "+v"(ux[j]), "+v"(uy[j]));
+            };
+            issue(0);
+            if (DEPTH > 1)
+                issue(1);
+#pragma unroll
+            for (int j = 0; j < DEPTH; ++j) {
+                eval_sample(clampk(k0 + j), ((mflags >> j) & 1u) != 0u, ux[j], uy[j], __builtin_floor(ux[j]), __builtin_floor(uy[j]), qv[j]);
+                if (j + 2 < DEPTH)
+                    issue(j + 2);
+                if (j == (DEPTH >= 3 ? DEPTH - 3 : 0))
+                    late();
+            }
+          }
+        } else if (PIPE) {
+            late();  // no body: directly behind the decision
         }
 // census: loop: group bookkeeping (ballots, branches)
         return finish_check(k0, tn64, check_finished);
@@ -1154,9 +1213,16 @@ __device__ __forceinline__ bool march_tile(ArgPtr a, const int bl, const int qy,
         const double ta64 = tc0, tb64 = tc3;  // first / last table value of THIS group (tq of the previous call)
         tc0 = tq[0];
         tc3 = tq[DEPTH - 1];
-        prefetch(nxt);                 // group k0 + DEPTH
-        load_tq(k0 + 2 * DEPTH);       // ... and the table values of the one after it
-        return consume(k0, cur.m, cur.z, ta64, tb64, tc0, check_finished, std::false_type{}, false);
+        if (!PIPE) {
+            prefetch(nxt);                 // group k0 + DEPTH
+            load_tq(k0 + 2 * DEPTH);       // ... and the table values of the one after it
+            return consume(k0, cur.m, cur.z, ta64, tb64, tc0, check_finished, std::false_type{}, false, []() {});
+        }
+        // PIPE: decide first, prefetch late -- consume() requests the next group where its registers are free
+        return consume(k0, cur.m, cur.z, ta64, tb64, tc0, check_finished, std::false_type{}, false, [&]() {
+            prefetch(nxt);
+            load_tq(k0 + 2 * DEPTH);
+        });
     };
 
     if (ROUGH) {
@@ -1328,7 +1394,7 @@ __device__ __forceinline__ bool march_tile(ArgPtr a, const int bl, const int qy,
                     int cj, rj;
                     cm[j] = ALL_ONES ? 1u : buf_load_u8(mr, mask_offset(x64 + tj * dx64, y64 + tj * dy64, cj, rj));
                 }
-                if (!consume(k0, cm, zcur, ta64, tb64, tc0, check, std::true_type{}, cw))
+                if (!consume(k0, cm, zcur, ta64, tb64, tc0, check, std::true_type{}, cw, []() {}))
                     break;
                 zcur = record_of(tc0, tc3);  // (fetched again rather than kept in registers across the bodies)
                 continue;
