@@ -187,10 +187,13 @@ def check(status: int, what: str):
         raise GcfrError("%s failed: %s (%d)" % (what, _ERRORS.get(status, "unknown"), status))
 
 
+NO_CPU_PATH = "geomconsistentfr_amd has no CPU path: tensors must be on a ROCm device"
+
+
 def require_device(*tensors):
     for t in tensors:
         if t is not None and not t.is_cuda:
-            raise GcfrError("geomconsistentfr_amd has no CPU path: tensors must be on a ROCm device")
+            raise GcfrError(NO_CPU_PATH)
 
 
 def stream_ptr(device) -> int:
@@ -203,5 +206,80 @@ def ptr(t):
 
 
 def f32c(t):
-    """an upstream gradient as the kernels read it (f32, contiguous); None stays None"""
-    return None if t is None else t.to(torch.float32).contiguous()
+    """a tensor (an input, an upstream gradient) as the kernels read it: detached, f32, contiguous; None stays None"""
+    return None if t is None else t.detach().to(torch.float32).contiguous()
+
+
+STREAM = object()      # stands at the stream parameter's position in `launch`'s arguments
+
+
+def launch(name: str, device, *args):
+    """THE way a kernel entry is called: `args` in the order of the prototype in include/gcfr.h, with `STREAM` where the stream goes.
+    A tensor is passed as its address after it has been found on `device` (a ROCm device) and contiguous; None is NULL; ints,
+    floats, ctypes objects and computed addresses go through as given.  The call runs with `device` current, on its current
+    stream, and a status other than GCFR_OK raises.  Every refusal is a GcfrError naming the entry, before the entry is called:
+    the entries are cdecl, so ctypes itself would pass a list that is too long."""
+    want = _SIGNATURES[name][1]
+    if len(args) != len(want):
+        raise GcfrError("%s takes %d arguments (include/gcfr.h), got %d" % (name, len(want), len(args)))
+    device = torch.device(device)
+    if device.type == "cuda" and device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    call, at = list(args), None
+    for i, a in enumerate(args):
+        if isinstance(a, torch.Tensor):
+            if not a.is_cuda:
+                raise GcfrError("%s, argument %d: %s" % (name, i, NO_CPU_PATH))
+            if a.device != device:
+                raise GcfrError("%s, argument %d: a tensor on %s in a launch on %s" % (name, i, a.device, device))
+            if not a.is_contiguous():
+                raise GcfrError("%s, argument %d: a tensor %s with strides %s is not contiguous"
+                                % (name, i, tuple(a.shape), tuple(a.stride())))
+            call[i] = a.data_ptr()
+        elif a is STREAM:
+            at = i
+    fn = getattr(load(), name)
+    with torch.cuda.device(device):
+        if at is not None:
+            call[at] = torch.cuda.current_stream(device).cuda_stream
+        check(fn(*call), name)
+
+
+# ----------------------------------------------------------------------------------------------------------------------------
+# what the Python entries check BEFORE anything is loaded or launched, so that a mismatch never reaches a kernel
+# ----------------------------------------------------------------------------------------------------------------------------
+FLOATS = (torch.float16, torch.bfloat16, torch.float32, torch.float64)
+
+
+def check_tensors(what: str, named, one_device: bool = True, **dtypes):
+    """the (name, value) pairs of `named` are tensors -- f32, or `name=dtype` / `name=(dtype, ...)` -- and, with `one_device`, all
+    on the first one's device.  A value of None is an absent optional and is skipped.  Returns the tensors that are present."""
+    named = [(n, t) for n, t in named if t is not None]
+    for n, t in named:
+        if not torch.is_tensor(t):
+            raise GcfrError("%s: %s must be a tensor, got %s" % (what, n, type(t).__name__))
+    for n, t in named:
+        want = dtypes.get(n, torch.float32)
+        if t.dtype not in (want if isinstance(want, tuple) else (want,)):
+            names = " or ".join(str(d).replace("torch.", "") for d in (want if isinstance(want, tuple) else (want,)))
+            raise GcfrError("%s: %s must be %s, got %s" % (what, n, names, t.dtype))
+    if one_device and any(t.device != named[0][1].device for _, t in named):
+        raise GcfrError("%s: tensors on one device; got %s" % (what, ", ".join("%s on %s" % (n, t.device) for n, t in named)))
+    return [t for _, t in named]
+
+
+def check_shape(name: str, t, *shapes, why: str = ""):
+    """the shape of tensor `t` is one of `shapes`"""
+    if tuple(t.shape) not in shapes:
+        raise GcfrError("%s must be %s%s; got %s" % (name, " or ".join(str(tuple(s)).replace(" ", "") for s in shapes), why, tuple(t.shape)))
+
+
+def check_out(out, shape):
+    """`out` (None: absent) is a buffer the result can be written into: contiguous, of `shape`, and does not require a gradient
+    (its dtype and device are `check_tensors`')"""
+    if out is None:
+        return
+    if tuple(out.shape) != tuple(shape) or not out.is_contiguous():
+        raise GcfrError("out must be a contiguous %s tensor; got %s with strides %s" % (tuple(shape), tuple(out.shape), tuple(out.stride())))
+    if out.requires_grad:
+        raise GcfrError("out must not require a gradient: it is a buffer the result is written into")

@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import require_device as _require_device, stream_ptr as _stream_ptr
+from ._lib import STREAM, f32c, launch, require_device
 
 
 @dataclass(frozen=True)
@@ -66,22 +66,15 @@ def sample_table(params: RenderParams, device) -> torch.Tensor:
     return t
 
 
-def _f32c(t: torch.Tensor) -> torch.Tensor:
-    return t.detach().to(torch.float32).contiguous()
-
-
 def light_prep(light: torch.Tensor, params: RenderParams = RenderParams()):
     """(..., 3) raw / target light -> (unit direction, light point), same leading shape.  T8:357-363."""
-    _require_device(light)
-    L = _lib.load()
-    lr = _f32c(light).reshape(-1, 3)
+    require_device(light)
+    lr = f32c(light).reshape(-1, 3)
     unit = torch.empty_like(lr)
     pt = torch.empty_like(lr)
     clamp = params.clamp_light_z_min is not None
-    with torch.cuda.device(lr.device):
-        _lib.check(L.gcfr_light_prep(lr.data_ptr(), lr.shape[0], int(clamp),
-                                     float(params.clamp_light_z_min or 0.0), float(params.light_distance),
-                                     unit.data_ptr(), pt.data_ptr(), _stream_ptr(lr.device)), "gcfr_light_prep")
+    launch("gcfr_light_prep", lr.device, lr, lr.shape[0], int(clamp), float(params.clamp_light_z_min or 0.0),
+           float(params.light_distance), unit, pt, STREAM)
     return unit.reshape(light.shape), pt.reshape(light.shape)
 
 
@@ -101,16 +94,16 @@ def shadow_min_distance(depth: torch.Tensor, mask: torch.Tensor, light_pt: torch
     include/gcfr.h).  `params.pixels = "mask"` reaches the library as `options.pixels = 1`, lives in the training (argmin) march
     and therefore FORCES want_argmin: an argmin tensor is returned (and the five-wave argmin kernel runs) even if the caller
     passed want_argmin=False."""
-    _require_device(depth, mask, light_pt)
+    require_device(depth, mask, light_pt)
     if params.pixels != "all":
         if not use_workspace:
             raise _lib.GcfrError("RenderParams.pixels = %r needs the workspace path (use_workspace=True)" % (params.pixels,))
         want_argmin, options = _pixels_options(params, want_argmin, options)
     L_ = _lib.load()
-    depth = _f32c(depth)
+    depth = f32c(depth)
     B, H, W = depth.shape
     mask_u8 = mask_to_u8(mask).reshape(-1, H, W)
-    light_pt = _f32c(light_pt).reshape(B, -1, 3)
+    light_pt = f32c(light_pt).reshape(B, -1, 3)
     L = light_pt.shape[1]
     tt = sample_table(params, depth.device)
     md = torch.empty((B, L, H, W), dtype=torch.float32, device=depth.device)
@@ -118,12 +111,8 @@ def shadow_min_distance(depth: torch.Tensor, mask: torch.Tensor, light_pt: torch
     box = (ctypes_float4(params.bonus_box) if params.bonus_box is not None else None)
     ws_bytes = int(L_.gcfr_shadow_workspace_bytes(B, H, W)) if use_workspace else 0
     ws = torch.empty(ws_bytes, dtype=torch.uint8, device=depth.device) if ws_bytes else None
-    with torch.cuda.device(depth.device):
-        _lib.check(L_.gcfr_shadow_fwd(depth.data_ptr(), mask_u8.data_ptr(), mask_u8.shape[0], light_pt.data_ptr(),
-                                      B, L, H, W, params.n_samples, tt.data_ptr(), float(params.inside_bonus),
-                                      box, md.data_ptr(), am.data_ptr() if am is not None else None,
-                                      ws.data_ptr() if ws is not None else None, ws_bytes,
-                                      _stream_ptr(depth.device), _lib.opt_ref(options)), "gcfr_shadow_fwd")
+    launch("gcfr_shadow_fwd", depth.device, depth, mask_u8, mask_u8.shape[0], light_pt, B, L, H, W, params.n_samples, tt,
+           float(params.inside_bonus), box, md, am, ws, ws_bytes, STREAM, _lib.opt_ref(options))
     return md, am
 
 
@@ -134,26 +123,22 @@ def ctypes_float4(v):
 
 def shade(normals, depth, albedo, light_pt, ambient, min_dist, params: RenderParams = RenderParams()):
     """Replaces T8:364-369, 517-522.  Shapes as include/gcfr.h; returns dict of f32 tensors."""
-    _require_device(normals, depth, albedo, light_pt, ambient, min_dist)
-    L_ = _lib.load()
-    depth = _f32c(depth)
+    require_device(normals, depth, albedo, light_pt, ambient, min_dist)
+    depth = f32c(depth)
     B, H, W = depth.shape
-    normals = _f32c(normals).reshape(B, 3, H, W)
-    albedo = _f32c(albedo).reshape(B, 3, H, W)
-    light_pt = _f32c(light_pt).reshape(B, -1, 3)
+    normals = f32c(normals).reshape(B, 3, H, W)
+    albedo = f32c(albedo).reshape(B, 3, H, W)
+    light_pt = f32c(light_pt).reshape(B, -1, 3)
     L = light_pt.shape[1]
-    ambient = _f32c(ambient).reshape(B, L)
-    min_dist = _f32c(min_dist).reshape(B, L, H, W)
+    ambient = f32c(ambient).reshape(B, L)
+    min_dist = f32c(min_dist).reshape(B, L, H, W)
     dev = depth.device
     w = torch.empty((B, L, H, W), dtype=torch.float32, device=dev)
     full = torch.empty_like(w)
     fin = torch.empty_like(w)
     ren = torch.empty((B, L, 3, H, W), dtype=torch.float32, device=dev)
-    with torch.cuda.device(dev):
-        _lib.check(L_.gcfr_shade_fwd(normals.data_ptr(), depth.data_ptr(), albedo.data_ptr(), light_pt.data_ptr(),
-                                     ambient.data_ptr(), min_dist.data_ptr(), B, L, H, W,
-                                     float(params.directional_intensity), w.data_ptr(), full.data_ptr(),
-                                     fin.data_ptr(), ren.data_ptr(), _stream_ptr(dev)), "gcfr_shade_fwd")
+    launch("gcfr_shade_fwd", dev, normals, depth, albedo, light_pt, ambient, min_dist, B, L, H, W,
+           float(params.directional_intensity), w, full, fin, ren, STREAM)
     return dict(shadow_mask_weights=w, full_shading=full, final_shading=fin, rendered_images=ren)
 
 
@@ -303,16 +288,16 @@ def render_prepass(depth, mask, light, params: RenderParams = RenderParams(), wa
     `src`: the `source_signature()` of the caller's own tensors where a wrapper reshaped them before this call (default: of
     depth, mask, light as given); the march call must present the same signature -- a different tensor, or the same one written
     in place in between, is an error there, not a render of stale data."""
-    _require_device(depth, mask, light)
+    require_device(depth, mask, light)
     want_argmin, options = _pixels_options(params, want_argmin, options)
     L_ = _lib.load()
     if src is None:
         src = source_signature(depth, mask, light)
-    depth = _f32c(depth)
+    depth = f32c(depth)
     B, H, W = depth.shape
     dev = depth.device
     mask_u8 = mask_to_u8(mask).reshape(-1, H, W)
-    light = _f32c(light).reshape(B, -1, 3)
+    light = f32c(light).reshape(B, -1, 3)
     L = light.shape[1]
     fwd = _Forward(params, B, L, H, W, dev)
     p = Prepared()
@@ -348,7 +333,7 @@ def render_fwd(depth, mask, light, ambient, normals, albedo, params: RenderParam
     the prepass has been enqueued already (side stream), this call waits for it and enqueues the march only.  The caller's
     depth / mask / light are compared with what the prepass was given (`source_signature`: address, in-place version, shape,
     strides, dtype; `src` = the signature of the caller's own tensors where a wrapper reshaped them): a mismatch raises."""
-    _require_device(depth, mask, light, ambient, albedo)
+    require_device(depth, mask, light, ambient, albedo)
     if normals is None and camera is None:
         raise _lib.GcfrError("render_fwd needs either normals or camera=(fx, fy, cx, cy, z_offset)")
     want_argmin, options = _pixels_options(params, want_argmin, options)
@@ -365,17 +350,17 @@ def render_fwd(depth, mask, light, ambient, normals, albedo, params: RenderParam
         if prepared.key != _prepass_key((tuple(depth.shape), tuple(mask_u8.shape), tuple(light.shape)), params, options):
             raise _lib.GcfrError("render_fwd(prepared=...): params / options differ from the prepass call's")
     else:
-        depth = _f32c(depth)
+        depth = f32c(depth)
         B, H, W = depth.shape
         dev = depth.device
         mask_u8 = mask_to_u8(mask).reshape(-1, H, W)
-        light = _f32c(light).reshape(B, -1, 3)
+        light = f32c(light).reshape(B, -1, 3)
         L = light.shape[1]
-    ambient = _f32c(ambient).reshape(B, L)
+    ambient = f32c(ambient).reshape(B, L)
     if normals is not None:
-        _require_device(normals)
-        normals = _f32c(normals).reshape(B, 3, H, W)
-    albedo = _f32c(albedo).reshape(B, 3, H, W)
+        require_device(normals)
+        normals = f32c(normals).reshape(B, 3, H, W)
+    albedo = f32c(albedo).reshape(B, 3, H, W)
     # from NORMALS_KERNEL_MIN_LIGHTS lights per face: the light-independent stencil once, in its own launch, instead of once
     # per light in the march's epilogue (the same bits)
     fwd = _Forward(params, B, L, H, W, dev, camera if normals is None else None, normals_stage_for(L))
@@ -384,7 +369,7 @@ def render_fwd(depth, mask, light, ambient, normals, albedo, params: RenderParam
         torch.cuda.current_stream(dev).wait_event(prepared.event)     # the march starts behind the prepass
     bound = fwd.bind(light, depth, mask_u8, mask_u8.shape[0], normals, albedo, ambient, out, ws, ws_bytes)
     with torch.cuda.device(dev):
-        fwd(bound, _stream_ptr(dev), options, 0 if prepared is None else 2)
+        fwd(bound, _lib.stream_ptr(dev), options, 0 if prepared is None else 2)
     return out
 
 
@@ -462,11 +447,11 @@ class _RenderFunction(torch.autograd.Function):
     def forward(ctx, depth, albedo, light, ambient, normals, mask_u8, params):
         B, _, H, W = depth.shape
         L = light.shape[1]
-        depth3 = _f32c(depth).reshape(B, H, W)
-        light3 = _f32c(light).reshape(B, L, 3)
-        amb = _f32c(ambient).reshape(B, L)
-        albedo_c = _f32c(albedo)
-        normals_c = _f32c(normals)
+        depth3 = f32c(depth).reshape(B, H, W)
+        light3 = f32c(light).reshape(B, L, 3)
+        amb = f32c(ambient).reshape(B, L)
+        albedo_c = f32c(albedo)
+        normals_c = f32c(normals)
         need_grad = any(ctx.needs_input_grad[:5])
         out = render_fwd(depth3, mask_u8, light3, amb, normals_c, albedo_c, params, want_argmin=need_grad)
         unit, pt, md, am = out["unit_light_direction"], out["light_pt"], out["minimum_distance"], out["argmin"]
@@ -480,11 +465,10 @@ class _RenderFunction(torch.autograd.Function):
     def backward(ctx, g_w, g_full, g_fin, g_ren, g_unit, _g_md):
         depth3, albedo, light3, amb, normals, pt, md, am = ctx.saved_tensors
         prm = ctx.params
-        L_ = _lib.load()
         B, H, W = depth3.shape
         L = light3.shape[1]
         dev = depth3.device
-        gw, gfull, gfin, gren = [None if g is None else _f32c(g) for g in (g_w, g_full, g_fin, g_ren)]
+        gw, gfull, gfin, gren = [f32c(g) for g in (g_w, g_full, g_fin, g_ren)]
         grad_normals = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
         grad_albedo = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
         grad_depth = torch.zeros((B, H, W), dtype=torch.float32, device=dev)
@@ -492,30 +476,21 @@ class _RenderFunction(torch.autograd.Function):
         grad_amb = torch.zeros((B, L), dtype=torch.float64, device=dev)
         grad_md = torch.empty((B, L, H, W), dtype=torch.float32, device=dev)
         tt = sample_table(prm, dev)
-        with torch.cuda.device(dev):
-            st = _stream_ptr(dev)
-            _lib.check(L_.gcfr_shade_bwd(normals.data_ptr(), depth3.data_ptr(), albedo.data_ptr(), pt.data_ptr(),
-                                         amb.data_ptr(), md.data_ptr(), B, L, H, W, float(prm.directional_intensity),
-                                         _lib.ptr(gw), _lib.ptr(gfull), _lib.ptr(gfin), _lib.ptr(gren),
-                                         grad_normals.data_ptr(), grad_albedo.data_ptr(), grad_depth.data_ptr(),
-                                         grad_pt.data_ptr(), grad_amb.data_ptr(), grad_md.data_ptr(), st),
-                       "gcfr_shade_bwd")
-            _lib.check(L_.gcfr_shadow_bwd(grad_md.data_ptr(), depth3.data_ptr(), pt.data_ptr(), am.data_ptr(),
-                                          B, L, H, W, prm.n_samples, tt.data_ptr(), grad_depth.data_ptr(),
-                                          grad_pt.data_ptr(), st), "gcfr_shadow_bwd")
-            grad_light = _light_prep_bwd(light3, g_unit, grad_pt, prm, st)
+        launch("gcfr_shade_bwd", dev, normals, depth3, albedo, pt, amb, md, B, L, H, W, float(prm.directional_intensity),
+               gw, gfull, gfin, gren, grad_normals, grad_albedo, grad_depth, grad_pt, grad_amb, grad_md, STREAM)
+        launch("gcfr_shadow_bwd", dev, grad_md, depth3, pt, am, B, L, H, W, prm.n_samples, tt, grad_depth, grad_pt, STREAM)
+        grad_light = _light_prep_bwd(light3, g_unit, grad_pt, prm)
         return (grad_depth.reshape(B, 1, H, W), grad_albedo, grad_light, grad_amb.float(), grad_normals, None, None)
 
 
-def _light_prep_bwd(light3, g_unit, grad_pt, prm, st):
-    """gcfr_light_prep_bwd on stream `st`: the gradients of the unit direction (g_unit, any shape of B*L*3 elements, or None)
-    and of the light point (grad_pt (B,L,3) f64) -> the raw light's, (B,L,3) f32"""
+def _light_prep_bwd(light3, g_unit, grad_pt, prm):
+    """gcfr_light_prep_bwd: the gradients of the unit direction (g_unit, any shape of B*L*3 elements, or None) and of the light
+    point (grad_pt (B,L,3) f64) -> the raw light's, (B,L,3) f32"""
     B, L, _ = light3.shape
     grad_light = torch.empty((B, L, 3), dtype=torch.float32, device=light3.device)
-    gu = None if g_unit is None else _f32c(g_unit).reshape(B * L, 3)
-    _lib.check(_lib.load().gcfr_light_prep_bwd(light3.data_ptr(), B * L, int(prm.clamp_light_z_min is not None),
-                                               float(prm.clamp_light_z_min or 0.0), float(prm.light_distance), _lib.ptr(gu),
-                                               grad_pt.data_ptr(), grad_light.data_ptr(), st), "gcfr_light_prep_bwd")
+    gu = None if g_unit is None else f32c(g_unit).reshape(B * L, 3)
+    launch("gcfr_light_prep_bwd", light3.device, light3, B * L, int(prm.clamp_light_z_min is not None),
+           float(prm.clamp_light_z_min or 0.0), float(prm.light_distance), gu, grad_pt, grad_light, STREAM)
     return grad_light
 
 
@@ -532,7 +507,7 @@ def render(depth, albedo, light, ambient, normals, mask, params: RenderParams = 
     Returns the reference's tensors by name (T8:524 / S1:505), all f32; with (B,L,3) lights every per-light tensor carries a
     light axis after the batch axis (`_result_dict`).  Gradients flow to depth, albedo, light, ambient and normals through
     the HIP backward kernels (for L lights: summed over the lights where the input has no light axis)."""
-    _require_device(depth, albedo, light, ambient, normals, mask)
+    require_device(depth, albedo, light, ambient, normals, mask)
     B, _, H, W = depth.shape
     mask_u8 = mask_to_u8(mask).reshape(-1, H, W)
     light3, amb2, L, multi = _light_shapes(B, light, ambient)
@@ -554,7 +529,7 @@ class RenderFwdPlan:
         self.options = options          # _lib.Options or None; kept alive here, read by the library at every call
         dev = torch.device(device)
         if dev.type != "cuda":
-            raise _lib.GcfrError("RenderFwdPlan needs a HIP device (there is no CPU path); got %s" % dev)
+            raise _lib.GcfrError("RenderFwdPlan(device=%s): %s" % (dev, _lib.NO_CPU_PATH))
         if dev.index is None:
             dev = torch.device("cuda", torch.cuda.current_device())
         self.dev, self.params, self.shape, self.camera = dev, params, (B, L, H, W), camera
@@ -651,12 +626,12 @@ class _RenderFromDepthFunction(torch.autograd.Function):
     def forward(ctx, depth, albedo, light, ambient, mask, cam, params, prepared=None, src=None):
         B, _, H, W = depth.shape
         L = light.shape[1]
-        amb = _f32c(ambient).reshape(B, L)
-        albedo_c = _f32c(albedo)
+        amb = f32c(ambient).reshape(B, L)
+        albedo_c = f32c(albedo)
         need_grad = any(ctx.needs_input_grad[:4])
         if prepared is None:
-            depth3 = _f32c(depth).reshape(B, H, W)
-            light3 = _f32c(light).reshape(B, L, 3)
+            depth3 = f32c(depth).reshape(B, H, W)
+            light3 = f32c(light).reshape(B, L, 3)
             o = render_fwd(depth3, mask, light3, amb, None, albedo_c, params, want_argmin=need_grad, camera=cam)
         else:       # the march reads the prepass's own copies; the caller's tensors are only compared with its record
             o = render_fwd(depth.reshape(B, H, W), mask, light, amb, None, albedo_c, params, want_argmin=need_grad, camera=cam,
@@ -675,27 +650,20 @@ class _RenderFromDepthFunction(torch.autograd.Function):
     def backward(ctx, g_w, g_full, g_fin, g_ren, g_unit, g_nrm, _g_md):
         depth3, albedo, light3, amb, pt, md, am, nrm_fwd = ctx.saved_tensors
         prm, cam = ctx.params, ctx.cam
-        L_ = _lib.load()
         B, H, W = depth3.shape
         L = light3.shape[1]
         dev = depth3.device
-        gw, gfull, gfin, gren, gnrm = [None if g is None else _f32c(g) for g in (g_w, g_full, g_fin, g_ren, g_nrm)]
+        gw, gfull, gfin, gren, gnrm = [f32c(g) for g in (g_w, g_full, g_fin, g_ren, g_nrm)]
         grad_albedo = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
         grad_depth = torch.zeros((B, H, W), dtype=torch.float32, device=dev)
         grad_pt = torch.zeros((B, L, 3), dtype=torch.float64, device=dev)
         grad_amb = torch.zeros((B, L), dtype=torch.float64, device=dev)
         tt = sample_table(prm, dev)
         fx, fy, cx, cy, z_off = cam
-        with torch.cuda.device(dev):
-            st = _stream_ptr(dev)
-            _lib.check(L_.gcfr_render_bwd(depth3.data_ptr(), albedo.data_ptr(), pt.data_ptr(), amb.data_ptr(),
-                                          md.data_ptr(), am.data_ptr(), nrm_fwd.data_ptr(), B, L, H, W, prm.n_samples,
-                                          tt.data_ptr(),
-                                          fx, fy, cx, cy, z_off, 1, float(prm.directional_intensity),
-                                          _lib.ptr(gw), _lib.ptr(gfull), _lib.ptr(gfin), _lib.ptr(gren), _lib.ptr(gnrm),
-                                          grad_albedo.data_ptr(), grad_depth.data_ptr(), grad_pt.data_ptr(),
-                                          grad_amb.data_ptr(), st), "gcfr_render_bwd")
-            grad_light = _light_prep_bwd(light3, g_unit, grad_pt, prm, st)
+        launch("gcfr_render_bwd", dev, depth3, albedo, pt, amb, md, am, nrm_fwd, B, L, H, W, prm.n_samples, tt,
+               fx, fy, cx, cy, z_off, 1, float(prm.directional_intensity), gw, gfull, gfin, gren, gnrm,
+               grad_albedo, grad_depth, grad_pt, grad_amb, STREAM)
+        grad_light = _light_prep_bwd(light3, g_unit, grad_pt, prm)
         return (grad_depth.reshape(B, 1, H, W), grad_albedo, grad_light, grad_amb.float(), None, None, None, None, None)
 
 
@@ -741,7 +709,7 @@ def render_from_depth_prepass(depth, light, camera_matrix, mask, params: RenderP
     B, _, H, W = depth.shape
     if camera_scalars(camera_matrix) is None:
         return None
-    _require_device(depth, light, mask)
+    require_device(depth, light, mask)
     light3 = light if (light.dim() == 3 and light.shape[0] == B) else light.reshape(B, 1, 3)
     return render_prepass(depth.reshape(B, H, W), mask.reshape(-1, H, W), light3, params,
                           src=source_signature(depth, mask, light))
@@ -768,7 +736,7 @@ def render_from_depth(depth, albedo, light, ambient, camera_matrix, z_offset, ma
         r["surface_normals"] = normals
         return r
     cam = k4 + (float(z_offset),)
-    _require_device(depth, albedo, light, ambient, mask)
+    require_device(depth, albedo, light, ambient, mask)
     light3, amb2, L, multi = _light_shapes(B, light, ambient)
     src = source_signature(depth, mask, light) if prepared is not None else None
     mask3 = mask.reshape(-1, H, W)                 # (converted to u8 inside render_fwd; with `prepared` the prepass's copy is used)

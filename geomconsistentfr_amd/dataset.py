@@ -75,7 +75,7 @@ class RelightDataset:
         idx = np.asarray(indices, dtype=np.int64)
         dev = torch.device(device)
         if dev.type != "cuda":
-            raise _lib.GcfrError("geomconsistentfr_amd has no CPU path: RelightDataset.batch needs a ROCm device")
+            raise _lib.GcfrError("RelightDataset.batch(device=%s): %s" % (dev, _lib.NO_CPU_PATH))
         up = lambda a: torch.from_numpy(np.ascontiguousarray(a[idx])).to(dev, non_blocking=True)
         out = assemble_batch(up(self.images), up(self.masks), up(self.face_masks), up(self.albedo))
         out["lightings"] = up(self.lightings)
@@ -83,23 +83,23 @@ class RelightDataset:
         return out
 
 
+def _u8_on_device(what, *tensors):
+    if any(t.dtype != torch.uint8 for t in tensors):
+        raise _lib.GcfrError("%s: uint8 tensors; got %s" % (what, ", ".join(str(t.dtype) for t in tensors)))
+    _lib.require_device(*tensors)
+
+
 def assemble_batch(images_u8: torch.Tensor, depth_mask_u8: torch.Tensor, face_mask_u8: torch.Tensor,
                    albedo_u8: torch.Tensor) -> Dict[str, torch.Tensor]:
     """uint8 device tensors (B,H,W,3), (B,H,W) x 3 -> {images (B,H,W,3), masks, masks_fill, albedo (B,H,W,1)} f32, with the
     arithmetic of T8:550-556 and :610-615 (`gcfr_assemble_batch_u8`)."""
-    for t in (images_u8, depth_mask_u8, face_mask_u8, albedo_u8):
-        if not t.is_cuda or t.dtype != torch.uint8:
-            raise _lib.GcfrError("assemble_batch: uint8 tensors on a ROCm device (there is no CPU path)")
-    L_ = _lib.load()
+    _u8_on_device("assemble_batch", images_u8, depth_mask_u8, face_mask_u8, albedo_u8)
     x, dm, fm, al = (t.contiguous() for t in (images_u8, depth_mask_u8, face_mask_u8, albedo_u8))
     B, H, W, _ = x.shape
     f32 = dict(dtype=torch.float32, device=x.device)
     images = torch.empty((B, H, W, 3), **f32)
     masks, fill, albedo = (torch.empty((B, H, W, 1), **f32) for _ in range(3))
-    with torch.cuda.device(x.device):
-        _lib.check(L_.gcfr_assemble_batch_u8(x.data_ptr(), dm.data_ptr(), fm.data_ptr(), al.data_ptr(), B, H, W, images.data_ptr(),
-                                             masks.data_ptr(), fill.data_ptr(), albedo.data_ptr(),
-                                             torch.cuda.current_stream(x.device).cuda_stream), "gcfr_assemble_batch_u8")
+    _lib.launch("gcfr_assemble_batch_u8", x.device, x, dm, fm, al, B, H, W, images, masks, fill, albedo, _lib.STREAM)
     return dict(images=images, masks=masks, masks_fill=fill, albedo=albedo)
 
 
@@ -107,19 +107,13 @@ def masked_metrics(recon_u8: torch.Tensor, gt_u8: torch.Tensor, mask_u8: torch.T
     """MSE_MP.m:24 and DSSIM_MP_RGB.m:24-26 for B image pairs on the device: recon_u8, gt_u8 (B,H,W,3) uint8 RGB,
     mask_u8 (B|1,H,W) or (H,W) uint8.  Returns (mse (B,), dssim (B,)) float64 device tensors (`gcfr_masked_metrics_u8`;
     DSSIM follows MATLAB ssim()'s documented defaults -- unpinned, see include/gcfr.h)."""
-    for t in (recon_u8, gt_u8, mask_u8):
-        if not t.is_cuda or t.dtype != torch.uint8:
-            raise _lib.GcfrError("masked_metrics: uint8 tensors on a ROCm device (there is no CPU path)")
-    L_ = _lib.load()
+    _u8_on_device("masked_metrics", recon_u8, gt_u8, mask_u8)
     r, g = recon_u8.contiguous(), gt_u8.contiguous()
     B, H, W, _ = r.shape
     m = mask_u8.contiguous().reshape(-1, H, W)
-    ws_bytes = int(L_.gcfr_masked_metrics_workspace_bytes(B, H, W))
+    ws_bytes = int(_lib.load().gcfr_masked_metrics_workspace_bytes(B, H, W))
     ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=r.device)
     mse = torch.empty(B, dtype=torch.float64, device=r.device)
     dssim = torch.empty(B, dtype=torch.float64, device=r.device)
-    with torch.cuda.device(r.device):
-        _lib.check(L_.gcfr_masked_metrics_u8(r.data_ptr(), g.data_ptr(), m.data_ptr(), m.shape[0], B, H, W, mse.data_ptr(),
-                                             dssim.data_ptr(), ws.data_ptr(), ws_bytes,
-                                             torch.cuda.current_stream(r.device).cuda_stream), "gcfr_masked_metrics_u8")
+    _lib.launch("gcfr_masked_metrics_u8", r.device, r, g, m, m.shape[0], B, H, W, mse, dssim, ws, ws_bytes, _lib.STREAM)
     return mse, dssim

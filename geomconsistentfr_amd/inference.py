@@ -55,19 +55,12 @@ def _default_focal(transfer: bool, focal):
     return (700.0 if transfer else 1570.0) if focal is None else focal
 
 
-def _as_u8(m, device) -> torch.Tensor:
-    return (m if torch.is_tensor(m) else torch.as_tensor(np.asarray(m))).to(device=device, dtype=torch.uint8)
-
-
-def _as_lights(lights, device) -> torch.Tensor:
-    """light directions as an f32 device tensor (L,3) | (B,L,3)"""
-    t = (lights if torch.is_tensor(lights) else torch.as_tensor(np.asarray(lights, np.float32))).to(device=device, dtype=torch.float32)
-    return t.reshape(-1, 3) if t.dim() <= 2 else t
-
-
-def _as_batch(images) -> torch.Tensor:
-    x = images.to(torch.float32) if torch.is_tensor(images) else torch.as_tensor(np.asarray(images), dtype=torch.float32)
-    return x[None] if x.dim() == 3 else x
+def _as(a, device, dtype=torch.float32, single=None) -> torch.Tensor:
+    """`a` (a tensor, an array, nested numbers) as a `dtype` tensor on `device` (None: where it is); one of rank `single` is a
+    single item -- one photograph (H,W,3), one light (3,), one rig (L,3), one map (He,We,3) -- and gets a leading axis"""
+    t = (a if torch.is_tensor(a) else torch.as_tensor(np.asarray(a))).to(dtype)        # (converted where it is, then moved)
+    t = t[None] if t.dim() == single else t
+    return t if device is None else t.to(device)
 
 
 @torch.no_grad()
@@ -78,7 +71,7 @@ def relight_batch(model, images, masks_u8, lights, ambient: float = 0.5,
     the model uses (plus the model's ambient_offset); `ambient` only feeds the unused target argument, as in S1:588 (focal
     1570).  RelightNetLightingTransfer: `ambient` IS the target ambient (SLT:545; focal 700).
     Returns the model's 10- / 12-tuple (device tensors)."""
-    x = _as_batch(images).to(device)
+    x = _as(images, device, single=3)
     B, H, W, _ = x.shape
     mask = torch.as_tensor(np.asarray(masks_u8), dtype=torch.float64).reshape(H, W, 1) / 255.0     # S1:580
     tl = torch.as_tensor(np.asarray(lights), dtype=torch.float32).reshape(B, 3, 1, 1).to(device)
@@ -109,10 +102,9 @@ def relight_images(model, images, mask_u8, lights, ambient: float = 0.5, focal: 
     The script feeds the MODEL `curr_mask` (S1:586-588) and composites with the fill-nose-and-mouth mask
     (`curr_mask_fill_nose_3_channels`, S1:606-618); both are read from the same file in the shipped script (S1:564-567), so
     `composite_mask_u8` defaults to `mask_u8` -- pass the second mask when they differ."""
-    x = _as_batch(images).to(device)
+    x = _as(images, device, single=3)
     out = relight_batch(model, x, mask_u8, lights, ambient, focal, device)
-    mask = torch.as_tensor(np.asarray(mask_u8 if composite_mask_u8 is None else composite_mask_u8), dtype=torch.uint8,
-                           device=device)
+    mask = _as(mask_u8 if composite_mask_u8 is None else composite_mask_u8, device, torch.uint8)
     imgs = pp.inference_images_device(x, out[5], mask, mask_f32=_is_transfer(model))["rendered_image"]
     if fix_border:
         imgs = pp.fix_border_artifacts_device(imgs, mask)
@@ -124,13 +116,9 @@ def relight_lights_device(model, images, mask_u8, lights, ambient: float = 0.5, 
                           fix_border: bool = False, composite_mask_u8=None, epoch: int = 200) -> torch.Tensor:
     """`relight_lights` up to the bytes ON THE DEVICE: (B,L,H,W,3) uint8 tensor, nothing copied back.  `images` / `mask_u8` /
     `lights` may already be device tensors (then nothing is uploaded either): what bench.py's `relight_e2e` leg times."""
-    x = _as_batch(images).to(device)
+    x = _as(images, device, single=3)
     out, cm, transfer = _lights_pass(model, x, mask_u8, lights, ambient, focal, device, composite_mask_u8, epoch)
-    imgs = pp.inference_images_device(x, out[5], cm, mask_f32=transfer)["rendered_image"]                        # (B,L,H,W,3)
-    if fix_border:
-        B, L, H, W, _ = imgs.shape
-        imgs = pp.fix_border_artifacts_device(imgs.reshape(B * L, H, W, 3), cm).reshape(B, L, H, W, 3)
-    return imgs
+    return _light_composites(x, out, cm, transfer, fix_border)
 
 
 @torch.no_grad()
@@ -146,10 +134,14 @@ def relight_lights(model, images, mask_u8, lights, ambient: float = 0.5, focal: 
     return relight_lights_device(model, images, mask_u8, lights, ambient, focal, device, fix_border, composite_mask_u8, epoch).cpu().numpy()
 
 
-def _as_light_rgb(light_rgb, device) -> torch.Tensor:
-    """a rig's colour x weight per light as a contiguous f32 device tensor (1|B,L,3); (L,3) is one rig shared by all faces"""
-    t = (light_rgb if torch.is_tensor(light_rgb) else torch.as_tensor(np.asarray(light_rgb, np.float32))).to(device=device, dtype=torch.float32)
-    return (t[None] if t.dim() == 2 else t).contiguous()
+def _light_composites(x, out, cm, transfer: bool, fix_border: bool) -> torch.Tensor:
+    """`forward_lights`' tuple -> (B,L,H,W,3) uint8: the image kernel on its rendered images (out[5]), one launch over all B L
+    composites, and the optional border fix on the (B L,H,W,3) view"""
+    imgs = pp.inference_images_device(x, out[5], cm, mask_f32=transfer)["rendered_image"]
+    if fix_border:
+        B, L, H, W, _ = imgs.shape
+        imgs = pp.fix_border_artifacts_device(imgs.reshape(B * L, H, W, 3), cm).reshape(B, L, H, W, 3)
+    return imgs
 
 
 def _rig_composites(x, out, cm, light_rgb, transfer: bool, fix_border: bool) -> torch.Tensor:
@@ -165,9 +157,9 @@ def relight_rig_device(model, images, mask_u8, lights, light_rgb, ambient: float
                        fix_border: bool = False, composite_mask_u8=None, epoch: int = 200) -> torch.Tensor:
     """`relight_rig` up to the bytes ON THE DEVICE: (B,H,W,3) uint8 tensor, nothing copied back.  `images` / `mask_u8` / `lights` /
     `light_rgb` may already be device tensors."""
-    x = _as_batch(images).to(device)
+    x = _as(images, device, single=3)
     out, cm, transfer = _lights_pass(model, x, mask_u8, lights, ambient, focal, device, composite_mask_u8, epoch)
-    return _rig_composites(x, out, cm, _as_light_rgb(light_rgb, x.device), transfer, fix_border)
+    return _rig_composites(x, out, cm, _as(light_rgb, x.device, single=2).contiguous(), transfer, fix_border)
 
 
 @torch.no_grad()
@@ -188,7 +180,7 @@ def _as_photographs(photos_u8, device) -> torch.Tensor:
     t = photos_u8 if torch.is_tensor(photos_u8) else torch.as_tensor(np.asarray(photos_u8))
     if t.dtype != torch.uint8:
         raise GcfrError("photographs must be uint8 (0..255), got %s" % t.dtype)
-    return (t[None] if t.dim() == 3 else t).to(device)
+    return _as(t, device, torch.uint8, single=3)
 
 
 @torch.no_grad()
@@ -226,7 +218,7 @@ def relight_rig_fullres_device(model, photos_u8, mask_u8, lights, light_rgb, sca
     photos = _as_photographs(photos_u8, device)
     x = pp.ingest_photographs_device(photos, scale)
     out, cm, _transfer = _lights_pass(model, x, mask_u8, lights, ambient, focal, device, composite_mask_u8, epoch)
-    rendered, _ = combine_lights(out[8], out[0], _as_light_rgb(light_rgb, x.device))
+    rendered, _ = combine_lights(out[8], out[0], _as(light_rgb, x.device, single=2).contiguous())
     return pp.fullres_composites_device(photos, x, rendered, cm, scale, detail_clamp, floor)
 
 
@@ -240,13 +232,6 @@ def relight_rig_fullres(model, photos_u8, mask_u8, lights, light_rgb, scale: int
     the composite equals `relight_lights_fullres(...)[:, 0]`.  One device-to-host copy of B*H*W*3 bytes at the end."""
     return relight_rig_fullres_device(model, photos_u8, mask_u8, lights, light_rgb, scale, ambient, focal, device, composite_mask_u8,
                                       epoch, detail_clamp, floor).cpu().numpy()
-
-
-def _as_light_rgb_frames(light_rgb_frames, device) -> torch.Tensor:
-    """F rigs' colour x weight per light as a contiguous f32 device tensor (1|B,F,L,3); (F,L,3) is the same rigs for all faces"""
-    t = (light_rgb_frames if torch.is_tensor(light_rgb_frames) else torch.as_tensor(np.asarray(light_rgb_frames, np.float32)))
-    t = t.to(device=device, dtype=torch.float32)
-    return (t[None] if t.dim() == 3 else t).contiguous()
 
 
 def _rig_frames(x, out, cm, light_rgb_frames, transfer: bool, fix_border: bool) -> torch.Tensor:
@@ -264,9 +249,9 @@ def relight_rig_frames_device(model, images, mask_u8, lights, light_rgb_frames, 
                               device="cuda", fix_border: bool = False, composite_mask_u8=None, epoch: int = 200) -> torch.Tensor:
     """`relight_rig_frames` up to the bytes ON THE DEVICE: (B,F,H,W,3) uint8 tensor, nothing copied back.  `images` / `mask_u8` /
     `lights` / `light_rgb_frames` may already be device tensors."""
-    x = _as_batch(images).to(device)
+    x = _as(images, device, single=3)
     out, cm, transfer = _lights_pass(model, x, mask_u8, lights, ambient, focal, device, composite_mask_u8, epoch)
-    return _rig_frames(x, out, cm, _as_light_rgb_frames(light_rgb_frames, x.device), transfer, fix_border)
+    return _rig_frames(x, out, cm, _as(light_rgb_frames, x.device, single=3).contiguous(), transfer, fix_border)
 
 
 @torch.no_grad()
@@ -282,12 +267,6 @@ def relight_rig_frames(model, images, mask_u8, lights, light_rgb_frames, ambient
                                      composite_mask_u8, epoch).cpu().numpy()
 
 
-def _as_environment(env, device) -> torch.Tensor:
-    """a lat-long radiance map as a contiguous f32 device tensor (1|B,He,We,3); (He,We,3) is one map shared by all faces"""
-    t = (env if torch.is_tensor(env) else torch.as_tensor(np.asarray(env, np.float32))).to(device=device, dtype=torch.float32)
-    return (t[None] if t.dim() == 3 else t).contiguous()
-
-
 def _environment_directions(n_lights, min_z, device) -> torch.Tensor:
     return torch.from_numpy(sphere_directions(n_lights, min_z)).to(device)
 
@@ -300,11 +279,18 @@ def _lights_pass(model, x, mask_u8, lights, ambient, focal, device, composite_ma
     B, H, W, _ = x.shape
     transfer = _is_transfer(model)
     K = camera_matrix(_default_focal(transfer, focal), H, W)                                                     # host: read without a sync
-    m_u8 = _as_u8(mask_u8, device)
+    m_u8 = _as(mask_u8, device, torch.uint8)
     mask = (m_u8.to(torch.float64).reshape(H, W, 1) / 255.0)                                                     # S1:580 / SLT:540
-    lights = _as_lights(lights, device)
-    out = model.forward_lights(x, epoch, K, mask, lights, float(ambient)) if transfer else model.forward_lights(x, epoch, K, mask, lights)
-    return out, (m_u8 if composite_mask_u8 is None else _as_u8(composite_mask_u8, device)), transfer
+    out = _forward_lights(model, x, epoch, K, mask, _as(lights, device, single=1), float(ambient))
+    return out, (m_u8 if composite_mask_u8 is None else _as(composite_mask_u8, device, torch.uint8)), transfer
+
+
+def _forward_lights(model, x, epoch, K, mask, lights, ambient, hoist=None):
+    """`model.forward_lights` on operands that are already built (`_lights_pass` builds them per call, `RelightSession` once);
+    `ambient` reaches a RelightNetLightingTransfer only -- a RelightNetSingleImage reads its own (S1:342)"""
+    if _is_transfer(model):
+        return model.forward_lights(x, epoch, K, mask, lights, ambient, hoist=hoist)
+    return model.forward_lights(x, epoch, K, mask, lights, hoist=hoist)
 
 
 @torch.no_grad()
@@ -313,9 +299,9 @@ def relight_environment_device(model, images, mask_u8, env, n_lights: int = 64, 
                                fix_border: bool = False, composite_mask_u8=None, epoch: int = 200) -> torch.Tensor:
     """`relight_environment` up to the bytes ON THE DEVICE: (B,H,W,3) uint8 tensor, nothing copied back.  `images` / `mask_u8` /
     `env` / `rotation` may already be device tensors."""
-    x = _as_batch(images).to(device)
+    x = _as(images, device, single=3)
     directions = _environment_directions(n_lights, min_z, x.device)
-    env_d = _as_environment(env, x.device)
+    env_d = _as(env, x.device, single=3).contiguous()
     rot = None if rotation is None else torch.as_tensor(rotation, dtype=torch.float32)
     _check_environment(env_d, directions, rot, None, faces=x.shape[0])                # a malformed map fails before the network pass
     out, cm, transfer = _lights_pass(model, x, mask_u8, directions, ambient, focal, device, composite_mask_u8, epoch)
@@ -352,12 +338,12 @@ def relight_environment_frames(model, images, mask_u8, env, rotations, n_lights:
     `fused=True`: the same bytes from the same pass and the same F matmuls, then one stack, ONE cell-map launch and ONE
     integration launch for all frames (`lighting.environment_lights_frames`), ONE rig-frames launch (`lighting.rig_frames_u8`),
     and one more with `fix_border` -- no per-frame launch and no f32 image per frame."""
-    x = _as_batch(images).to(device)
+    x = _as(images, device, single=3)
     directions = _environment_directions(n_lights, min_z, x.device)
     rots = torch.as_tensor(rotations, dtype=torch.float32).to(x.device)
     if rots.dim() != 3 or tuple(rots.shape[1:]) != (3, 3) or rots.shape[0] < 1:
         raise GcfrError("rotations must be (F,3,3) with F >= 1; got %s" % (tuple(rots.shape),))
-    env_d = _as_environment(env, x.device)
+    env_d = _as(env, x.device, single=3).contiguous()
     _check_environment(env_d, directions, None, None, faces=x.shape[0])               # a malformed map fails before the network pass
     out, cm, transfer = _lights_pass(model, x, mask_u8, directions, ambient, focal, device, composite_mask_u8, epoch)
     if fused:
@@ -378,7 +364,7 @@ def capture_rig(model, reference_images, mask_u8, lights, ridge: float = 1e-3, s
     host synchronisation; it is what `relight_rig(_device)` and `RelightSession(light_rgb=...)` take.  `ridge` / `shared`: see
     `fit_light_rgb`, which also says why entries may be negative; `nonnegative=True` fits under light_rgb >= 0 instead (see there).
     `model` / `ambient` / `focal` as in `relight_lights`."""
-    x = _as_batch(reference_images).to(device)
+    x = _as(reference_images, device, single=3)
     n = (lights.shape if torch.is_tensor(lights) else np.asarray(lights).shape)
     L = n[-2] if len(n) >= 2 else 1
     if not 1 <= L <= MAX_FIT_LIGHTS:                                                  # a rig too large fails before the network pass
@@ -470,11 +456,11 @@ class RelightSession:
         self.model, self.device, self.epoch, self.ambient, self.fix_border = model, torch.device(device), epoch, float(ambient), fix_border
         self.transfer = _is_transfer(model)
         self.K = camera_matrix(_default_focal(self.transfer, focal), H, W)                                   # host
-        self.m_u8 = _as_u8(mask_u8, self.device).reshape(H, W)
-        self.cm = self.m_u8 if composite_mask_u8 is None else _as_u8(composite_mask_u8, self.device).reshape(H, W)
+        self.m_u8 = _as(mask_u8, self.device, torch.uint8).reshape(H, W)
+        self.cm = self.m_u8 if composite_mask_u8 is None else _as(composite_mask_u8, self.device, torch.uint8).reshape(H, W)
         self.mask = (self.m_u8.to(torch.float64).reshape(H, W, 1) / 255.0)
-        self.lights = _as_lights(lights, self.device).contiguous()
-        self.light_rgb = None if light_rgb is None else _as_light_rgb(light_rgb, self.device)     # a rig: one composite per face
+        self.lights = _as(lights, self.device, single=1).contiguous()
+        self.light_rgb = None if light_rgb is None else _as(light_rgb, self.device, single=2).contiguous()   # a rig: one composite per face
         self.x = torch.zeros((B, H, W, 3), dtype=torch.float32, device=self.device)
         self.ambient_dev = torch.full((1,), self.ambient, dtype=torch.float32, device=self.device)   # (no host-to-device copy inside the capture)
         self.out = None
@@ -499,29 +485,19 @@ class RelightSession:
 
     @torch.no_grad()
     def _pass(self):
-        hoist = self.model.hoist_prepass
-        self.model.hoist_prepass = hoist and self.graph is None and not torch.cuda.is_current_stream_capturing()
-        try:                                                  # (inside a graph there is no launch latency for a side stream to hide)
-            if self.transfer:
-                o = self.model.forward_lights(self.x, self.epoch, self.K, self.mask, self.lights, self.ambient_dev)
-            else:
-                o = self.model.forward_lights(self.x, self.epoch, self.K, self.mask, self.lights)
-        finally:
-            self.model.hoist_prepass = hoist
+        # inside a graph there is no launch latency for a side stream to hide: no hoisted prepass there (None: the model's own choice)
+        hoist = False if (self.graph is not None or torch.cuda.is_current_stream_capturing()) else None
+        o = _forward_lights(self.model, self.x, self.epoch, self.K, self.mask, self.lights, self.ambient_dev, hoist=hoist)
         if self.light_rgb is not None:
             return _rig_composites(self.x, o, self.cm, self.light_rgb, self.transfer, self.fix_border)
-        imgs = pp.inference_images_device(self.x, o[5], self.cm, mask_f32=self.transfer)["rendered_image"]
-        if self.fix_border:
-            B, L, H, W, _ = imgs.shape
-            imgs = pp.fix_border_artifacts_device(imgs.reshape(B * L, H, W, 3), self.cm).reshape(B, L, H, W, 3)
-        return imgs
+        return _light_composites(self.x, o, self.cm, self.transfer, self.fix_border)
 
     @torch.no_grad()
     def run(self, images=None) -> torch.Tensor:
         """images (B,H,W,3) f32 in [0,1] (host or device; None = whatever the static input holds) -> (B,L,H,W,3) uint8 DEVICE
         tensor ((B,H,W,3) for a session built with `light_rgb`); with a graph it is overwritten by the next run."""
         if images is not None:
-            self.x.copy_(_as_batch(images), non_blocking=True)
+            self.x.copy_(_as(images, None, single=3), non_blocking=True)
         if self.graph is None:
             return self._pass()
         self.graph.replay()
@@ -534,7 +510,7 @@ def lighting_transfer(model: RelightNetLightingTransfer, input_image, reference_
     """SLT:535-579: pass 1 on the reference image with a zero target light reads the estimated light and ambient
     (SLT:543); pass 2 relights the input image with them (SLT:545).  Returns the six images SLT:574-579 writes
     (uint8 RGB / single channel, composited and quantised on the device) plus the estimated light."""
-    xin, xref = _as_batch(input_image).to(device), _as_batch(reference_image).to(device)
+    xin, xref = _as(input_image, device, single=3), _as(reference_image, device, single=3)
     _, H, W, _ = xin.shape
     K = camera_matrix(focal, H, W, device)
     mask = (torch.as_tensor(np.asarray(mask_u8), dtype=torch.float64).reshape(H, W, 1) / 255.0).to(device)

@@ -46,30 +46,12 @@ from .block import RenderParams, render_from_depth
 MAX_LIGHTS = 4096      # include/gcfr.h: 1 <= L <= 4096
 
 
-def _launch_fwd(final, albedo, rgb, rendered, shading):
-    B, L, H, W = final.shape
-    dev = final.device
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().gcfr_light_rig_fwd(final.data_ptr(), albedo.data_ptr(), rgb.data_ptr(), rgb.shape[0], B, L, H, W,
-                                                  rendered.data_ptr(), shading.data_ptr(), _lib.stream_ptr(dev)),
-                   "gcfr_light_rig_fwd")
-
-
-def _launch_bwd(final, albedo, rgb, g_rendered, g_shading, g_final, g_albedo, g_rgb):
-    B, L, H, W = final.shape
-    dev = final.device
-    ptr = _lib.ptr
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().gcfr_light_rig_bwd(final.data_ptr(), albedo.data_ptr(), rgb.data_ptr(), rgb.shape[0], B, L, H, W,
-                                                  ptr(g_rendered), ptr(g_shading), ptr(g_final), ptr(g_albedo), ptr(g_rgb),
-                                                  _lib.stream_ptr(dev)), "gcfr_light_rig_bwd")
-
-
 class _CombineLightsFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, final, albedo, rgb):
         rendered, shading = torch.empty_like(albedo), torch.empty_like(albedo)
-        _launch_fwd(final, albedo, rgb, rendered, shading)
+        B, L, H, W = final.shape
+        _lib.launch("gcfr_light_rig_fwd", final.device, final, albedo, rgb, rgb.shape[0], B, L, H, W, rendered, shading, _lib.STREAM)
         ctx.save_for_backward(final, albedo, rgb)
         ctx.set_materialize_grads(False)          # an unused output's gradient arrives as None -> NULL, not as a tensor of zeros
         return rendered, shading
@@ -85,35 +67,30 @@ class _CombineLightsFunction(torch.autograd.Function):
         g_final = torch.empty_like(final) if want_final else None
         g_albedo = torch.empty_like(albedo) if want_albedo else None
         g_rgb = torch.zeros(rgb.shape, dtype=torch.float64, device=rgb.device) if want_rgb else None      # accumulated in f64
-        _launch_bwd(final, albedo, rgb, _lib.f32c(g_rendered), _lib.f32c(g_shading), g_final, g_albedo, g_rgb)
+        B, L, H, W = final.shape
+        _lib.launch("gcfr_light_rig_bwd", final.device, final, albedo, rgb, rgb.shape[0], B, L, H, W, _lib.f32c(g_rendered),
+                    _lib.f32c(g_shading), g_final, g_albedo, g_rgb, _lib.STREAM)
         return g_final, g_albedo, (g_rgb.float() if want_rgb else None)
 
 
-def _check_combine(final_shading, albedo, light_rgb):
-    """Every shape, dtype and device BEFORE anything is launched or loaded: a mismatch never reaches the kernel."""
-    names = ("final_shading", "albedo", "light_rgb")
-    tensors = (final_shading, albedo, light_rgb)
-    for n, t in zip(names, tensors):
-        if not torch.is_tensor(t):
-            raise _lib.GcfrError("combine_lights: %s must be a tensor, got %s" % (n, type(t).__name__))
-    for n, t in zip(names, tensors):
-        if t.dtype != torch.float32:
-            raise _lib.GcfrError("combine_lights: %s must be float32, got %s" % (n, t.dtype))
-    if any(t.device != final_shading.device for t in tensors):
-        raise _lib.GcfrError("combine_lights: tensors on one device; got %s" % ", ".join(str(t.device) for t in tensors))
+def _many_lights(final_shading, max_lights):
+    """-> (B, L, H, W) of a many-lights `final_shading`, each at least 1 and L at the most `max_lights`"""
     if final_shading.dim() != 4:
         raise _lib.GcfrError("final_shading must be (B,L,H,W) -- the many-lights form, with its light axis; got %s"
                              % (tuple(final_shading.shape),))
     B, L, H, W = final_shading.shape
-    if B < 1 or H < 1 or W < 1 or not 1 <= L <= MAX_LIGHTS:
-        raise _lib.GcfrError("final_shading (B,L,H,W) = %s: B, H, W >= 1 and 1 <= L <= %d" % (tuple(final_shading.shape), MAX_LIGHTS))
-    if tuple(albedo.shape) != (B, 3, H, W):
-        raise _lib.GcfrError("albedo must be %s (per face, no light axis) for final_shading %s; got %s"
-                             % ((B, 3, H, W), tuple(final_shading.shape), tuple(albedo.shape)))
-    if light_rgb.dim() != 3 or tuple(light_rgb.shape[1:]) != (L, 3) or light_rgb.shape[0] not in (1, B):
-        raise _lib.GcfrError("light_rgb must be (%d,%d,3) or (1,%d,3) for final_shading %s; got %s"
-                             % (B, L, L, tuple(final_shading.shape), tuple(light_rgb.shape)))
-    _lib.require_device(final_shading)
+    if B < 1 or H < 1 or W < 1 or not 1 <= L <= max_lights:
+        raise _lib.GcfrError("final_shading (B,L,H,W) = %s: B, H, W >= 1 and 1 <= L <= %d" % (tuple(final_shading.shape), max_lights))
+    return B, L, H, W
+
+
+def _check_combine(final_shading, albedo, light_rgb):
+    """Every shape, dtype and device BEFORE anything is launched or loaded: a mismatch never reaches the kernel."""
+    tensors = _lib.check_tensors("combine_lights", [("final_shading", final_shading), ("albedo", albedo), ("light_rgb", light_rgb)])
+    B, L, H, W = _many_lights(final_shading, MAX_LIGHTS)
+    _lib.check_shape("albedo", albedo, (B, 3, H, W), why=" (per face, no light axis) for final_shading %s" % (tuple(final_shading.shape),))
+    _lib.check_shape("light_rgb", light_rgb, (B, L, 3), (1, L, 3), why=" for final_shading %s" % (tuple(final_shading.shape),))
+    _lib.require_device(*tensors)
 
 
 def combine_lights(final_shading: torch.Tensor, albedo: torch.Tensor, light_rgb: torch.Tensor):
@@ -263,29 +240,6 @@ def _device_tables(He, We, device):
     return _ENV_TABLES[key]
 
 
-def _launch_env_cells(rows, cols, dirs_map, He, We, min_cos, cell):
-    dev = dirs_map.device
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().gcfr_environment_cells(rows.data_ptr(), cols.data_ptr(), dirs_map.data_ptr(), He, We, dirs_map.shape[0],
-                                                      float(min_cos), cell.data_ptr(), _lib.stream_ptr(dev)), "gcfr_environment_cells")
-
-
-def _launch_env_fwd(env, row_w, cell, L, rgb):
-    E, He, We, _ = env.shape
-    dev = env.device
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().gcfr_environment_fwd(env.data_ptr(), E, He, We, row_w.data_ptr(), cell.data_ptr(), L, rgb.data_ptr(),
-                                                    _lib.stream_ptr(dev)), "gcfr_environment_fwd")
-
-
-def _launch_env_bwd(g_rgb, row_w, cell, g_env):
-    E, He, We, _ = g_env.shape
-    dev = g_env.device
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().gcfr_environment_bwd(g_rgb.data_ptr(), row_w.data_ptr(), cell.data_ptr(), E, He, We, g_rgb.shape[1],
-                                                    g_env.data_ptr(), _lib.stream_ptr(dev)), "gcfr_environment_bwd")
-
-
 class _EnvironmentLightsFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, env, dirs_map, min_cos, out):
@@ -294,8 +248,8 @@ class _EnvironmentLightsFunction(torch.autograd.Function):
         rows, row_w, cols = _device_tables(He, We, env.device)
         cell = torch.empty((He, We), dtype=torch.int32, device=env.device)
         rgb = torch.empty((E, L, 3), dtype=torch.float32, device=env.device) if out is None else out
-        _launch_env_cells(rows, cols, dirs_map, He, We, min_cos, cell)
-        _launch_env_fwd(env, row_w, cell, L, rgb)
+        _lib.launch("gcfr_environment_cells", env.device, rows, cols, dirs_map, He, We, L, float(min_cos), cell, _lib.STREAM)
+        _lib.launch("gcfr_environment_fwd", env.device, env, E, He, We, row_w, cell, L, rgb, _lib.STREAM)
         ctx.save_for_backward(row_w, cell)
         ctx.env_shape = tuple(env.shape)
         if out is not None:
@@ -308,20 +262,18 @@ class _EnvironmentLightsFunction(torch.autograd.Function):
         if g_rgb is None or not ctx.needs_input_grad[0]:
             return None, None, None, None
         g_env = torch.empty(ctx.env_shape, dtype=torch.float32, device=cell.device)
-        _launch_env_bwd(_lib.f32c(g_rgb), row_w, cell, g_env)
+        E, He, We, _ = ctx.env_shape
+        g_rgb = _lib.f32c(g_rgb)
+        _lib.launch("gcfr_environment_bwd", cell.device, g_rgb, row_w, cell, E, He, We, g_rgb.shape[1], g_env, _lib.STREAM)
         return g_env, None, None, None          # (no gradient to the directions: the cell map is piecewise constant in them)
 
 
 def _check_environment(env, directions, rotation, out, faces=None, frames=None):
     """Every shape, dtype and device BEFORE anything is launched or loaded: a mismatch never reaches the kernels.  `faces`: the
-    batch the maps are for (E must be 1 or that).  `frames`: `out` is the frames form's, (E,frames,L,3)."""
-    named = [("env", env), ("directions", directions)] + ([("rotation", rotation)] if rotation is not None else []) \
-        + ([("out", out)] if out is not None else [])
-    for n, t in named:
-        if not torch.is_tensor(t):
-            raise _lib.GcfrError("environment_lights: %s must be a tensor, got %s" % (n, type(t).__name__))
-        if t.dtype != torch.float32:
-            raise _lib.GcfrError("environment_lights: %s must be float32, got %s" % (n, t.dtype))
+    batch the maps are for (E must be 1 or that).  `frames`: `out` is the frames form's, (E,frames,L,3).  `rotation` may be a
+    host tensor (it is uploaded), so it is held to no device."""
+    _lib.check_tensors("environment_lights", [("env", env), ("directions", directions), ("out", out)])
+    _lib.check_tensors("environment_lights", [("rotation", rotation)])
     if env.dim() != 4 or env.shape[3] != 3:
         raise _lib.GcfrError("env must be (E,He,We,3) -- a lat-long map per face, or E = 1 for one map; got %s" % (tuple(env.shape),))
     E, He, We, _ = env.shape
@@ -331,17 +283,10 @@ def _check_environment(env, directions, rotation, out, faces=None, frames=None):
         raise _lib.GcfrError("env must be (1,He,We,3) or (%d,He,We,3) for %d faces; got %s" % (faces, faces, tuple(env.shape)))
     if directions.dim() != 2 or directions.shape[1] != 3 or not 1 <= directions.shape[0] <= MAX_LIGHTS:
         raise _lib.GcfrError("directions must be (L,3) with 1 <= L <= %d; got %s" % (MAX_LIGHTS, tuple(directions.shape)))
-    if rotation is not None and tuple(rotation.shape) != (3, 3):
-        raise _lib.GcfrError("rotation must be (3,3); got %s" % (tuple(rotation.shape),))
-    if directions.device != env.device:
-        raise _lib.GcfrError("environment_lights: env and directions on one device; got %s, %s" % (env.device, directions.device))
-    if out is not None:
-        want = (E, directions.shape[0], 3) if frames is None else (E, frames, directions.shape[0], 3)
-        if tuple(out.shape) != want or out.device != env.device or not out.is_contiguous():
-            raise _lib.GcfrError("out must be a contiguous %s tensor on %s; got %s on %s"
-                                 % (want, env.device, tuple(out.shape), out.device))
-        if out.requires_grad:
-            raise _lib.GcfrError("out must not require a gradient: it is a buffer the result is written into")
+    if rotation is not None:
+        _lib.check_shape("rotation", rotation, (3, 3))
+    L = directions.shape[0]
+    _lib.check_out(out, (E, L, 3) if frames is None else (E, frames, L, 3))
     _lib.require_device(env, directions, out)
 
 
@@ -401,41 +346,24 @@ RIG_FRAMES_TILE = 4        # csrc/gcfr_rig_frames.hip kFrameTile: frames per wor
 
 def _check_rig_frames(final_shading, albedo, images, mask_u8, light_rgb_frames, out):
     """Every tensor that is passed by pointer -- shape, dtype, device -- BEFORE anything is launched or loaded."""
-    named = [("final_shading", final_shading), ("albedo", albedo), ("images", images), ("mask_u8", mask_u8),
-             ("light_rgb_frames", light_rgb_frames)] + ([("out", out)] if out is not None else [])
-    for n, t in named:
-        if not torch.is_tensor(t):
-            raise _lib.GcfrError("rig_frames_u8: %s must be a tensor, got %s" % (n, type(t).__name__))
-        want = torch.uint8 if n in ("mask_u8", "out") else torch.float32
-        if t.dtype != want:
-            raise _lib.GcfrError("rig_frames_u8: %s must be %s, got %s" % (n, str(want).replace("torch.", ""), t.dtype))
-    if any(t.device != final_shading.device for _, t in named):
-        raise _lib.GcfrError("rig_frames_u8: tensors on one device; got %s" % ", ".join(str(t.device) for _, t in named))
-    if final_shading.dim() != 4:
-        raise _lib.GcfrError("final_shading must be (B,L,H,W) -- the many-lights form, with its light axis; got %s"
-                             % (tuple(final_shading.shape),))
-    B, L, H, W = final_shading.shape
-    if B < 1 or H < 1 or W < 1 or not 1 <= L <= MAX_LIGHTS:
-        raise _lib.GcfrError("final_shading (B,L,H,W) = %s: B, H, W >= 1 and 1 <= L <= %d" % (tuple(final_shading.shape), MAX_LIGHTS))
+    tensors = _lib.check_tensors("rig_frames_u8", [("final_shading", final_shading), ("albedo", albedo), ("images", images),
+                                                   ("mask_u8", mask_u8), ("light_rgb_frames", light_rgb_frames), ("out", out)],
+                                 mask_u8=torch.uint8, out=torch.uint8)
+    B, L, H, W = _many_lights(final_shading, MAX_LIGHTS)
+    of = " for final_shading %s" % (tuple(final_shading.shape),)
     if H * W >= 2 ** 31 or B * ((H * W + 1023) // 1024) >= 2 ** 31:
         raise _lib.GcfrError("final_shading (B,L,H,W) = %s: H W < 2^31 and B ceil(H W / 1024) < 2^31" % (tuple(final_shading.shape),))
-    if tuple(albedo.shape) != (B, 3, H, W):
-        raise _lib.GcfrError("albedo must be %s for final_shading %s; got %s" % ((B, 3, H, W), tuple(final_shading.shape), tuple(albedo.shape)))
-    if tuple(images.shape) != (B, H, W, 3):
-        raise _lib.GcfrError("images must be %s (the photographs, HWC) for final_shading %s; got %s"
-                             % ((B, H, W, 3), tuple(final_shading.shape), tuple(images.shape)))
-    if tuple(mask_u8.shape) not in ((H, W), (1, H, W), (B, H, W)):
-        raise _lib.GcfrError("mask_u8 must be (%d,%d,%d), (1,%d,%d) or (%d,%d); got %s" % (B, H, W, H, W, H, W, tuple(mask_u8.shape)))
+    _lib.check_shape("albedo", albedo, (B, 3, H, W), why=of)
+    _lib.check_shape("images", images, (B, H, W, 3), why=" (the photographs, HWC)" + of)
+    _lib.check_shape("mask_u8", mask_u8, (B, H, W), (1, H, W), (H, W))
     r = light_rgb_frames
     if r.dim() not in (3, 4) or tuple(r.shape[-2:]) != (L, 3) or (r.dim() == 4 and r.shape[0] not in (1, B)):
-        raise _lib.GcfrError("light_rgb_frames must be (F,%d,3), (1,F,%d,3) or (%d,F,%d,3) for final_shading %s; got %s"
-                             % (L, L, B, L, tuple(final_shading.shape), tuple(r.shape)))
+        raise _lib.GcfrError("light_rgb_frames must be (F,%d,3), (1,F,%d,3) or (%d,F,%d,3)%s; got %s" % (L, L, B, L, of, tuple(r.shape)))
     F = r.shape[-3]
     if not 1 <= F <= MAX_FRAMES:
         raise _lib.GcfrError("light_rgb_frames %s: 1 <= F <= %d frames" % (tuple(r.shape), MAX_FRAMES))
-    if out is not None and (tuple(out.shape) != (B, F, H, W, 3) or not out.is_contiguous()):
-        raise _lib.GcfrError("out must be a contiguous (%d,%d,%d,%d,3) uint8 tensor; got %s" % (B, F, H, W, tuple(out.shape)))
-    _lib.require_device(*[t for _, t in named])
+    _lib.check_out(out, (B, F, H, W, 3))
+    _lib.require_device(*tensors)
     return B, L, F, H, W
 
 
@@ -457,35 +385,13 @@ def rig_frames_u8(final_shading: torch.Tensor, albedo: torch.Tensor, images: tor
     m = mask_u8.contiguous().reshape(-1, H, W)
     rgb = light_rgb_frames.detach().contiguous().reshape(-1, F, L, 3)
     frames = torch.empty((B, F, H, W, 3), dtype=torch.uint8, device=dev) if out is None else out
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().gcfr_light_rig_frames_u8(final.data_ptr(), alb.data_ptr(), x.data_ptr(), m.data_ptr(), m.shape[0],
-                                                        int(bool(mask_f32)), rgb.data_ptr(), rgb.shape[0], B, L, F, H, W,
-                                                        frames.data_ptr(), _lib.stream_ptr(dev)), "gcfr_light_rig_frames_u8")
+    _lib.launch("gcfr_light_rig_frames_u8", dev, final, alb, x, m, m.shape[0], int(bool(mask_f32)), rgb, rgb.shape[0], B, L, F, H, W,
+                frames, _lib.STREAM)
     return frames
 
 
-def _launch_env_cells_frames(rows, cols, dirs_map, He, We, min_cos, cell):
-    F, L, _ = dirs_map.shape
-    dev = dirs_map.device
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().gcfr_environment_cells_frames(rows.data_ptr(), cols.data_ptr(), dirs_map.data_ptr(), F, He, We, L,
-                                                             float(min_cos), cell.data_ptr(), _lib.stream_ptr(dev)),
-                   "gcfr_environment_cells_frames")
-
-
-def _launch_env_fwd_frames(env, row_w, cell, L, rgb):
-    E, He, We, _ = env.shape
-    dev = env.device
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().gcfr_environment_fwd_frames(env.data_ptr(), E, He, We, row_w.data_ptr(), cell.data_ptr(), cell.shape[0],
-                                                           L, rgb.data_ptr(), _lib.stream_ptr(dev)), "gcfr_environment_fwd_frames")
-
-
 def _check_rotations(rotations):
-    if not torch.is_tensor(rotations):
-        raise _lib.GcfrError("environment_lights_frames: rotations must be a tensor, got %s" % type(rotations).__name__)
-    if rotations.dtype != torch.float32:
-        raise _lib.GcfrError("environment_lights_frames: rotations must be float32, got %s" % rotations.dtype)
+    _lib.check_tensors("environment_lights_frames", [("rotations", rotations)])
     if rotations.dim() != 3 or tuple(rotations.shape[1:]) != (3, 3) or not 1 <= rotations.shape[0] <= MAX_FRAMES:
         raise _lib.GcfrError("rotations must be (F,3,3) with 1 <= F <= %d; got %s" % (MAX_FRAMES, tuple(rotations.shape)))
 
@@ -513,8 +419,8 @@ def environment_lights_frames(env: torch.Tensor, directions: torch.Tensor, rotat
     rows, row_w, cols = _device_tables(He, We, dev)
     cell = torch.empty((F, He, We), dtype=torch.int32, device=dev)
     rgb = torch.empty((E, F, L, 3), dtype=torch.float32, device=dev) if out is None else out
-    _launch_env_cells_frames(rows, cols, dirs_map, He, We, min_cos, cell)
-    _launch_env_fwd_frames(env.detach().contiguous(), row_w, cell, L, rgb)
+    _lib.launch("gcfr_environment_cells_frames", dev, rows, cols, dirs_map, F, He, We, L, float(min_cos), cell, _lib.STREAM)
+    _lib.launch("gcfr_environment_fwd_frames", dev, env.detach().contiguous(), E, He, We, row_w, cell, F, L, rgb, _lib.STREAM)
     return rgb
 
 
@@ -536,44 +442,24 @@ def light_fit_geometry(B: int, H: int, W: int):
 
 def _check_fit(final_shading, albedo, image, weight, image_layout, out=None, shared=False, ridge=0.0, max_solves=0):
     """Every shape, dtype, device and range BEFORE anything is launched or loaded: a mismatch never reaches the kernels."""
-    named = [("final_shading", final_shading), ("albedo", albedo), ("image", image)] \
-        + ([("weight", weight)] if weight is not None else []) + ([("out", out)] if out is not None else [])
-    for n, t in named:
-        if not torch.is_tensor(t):
-            raise _lib.GcfrError("fit_light_rgb: %s must be a tensor, got %s" % (n, type(t).__name__))
-        if t.dtype != torch.float32 and not (n == "weight" and t.dtype == torch.uint8):
-            raise _lib.GcfrError("fit_light_rgb: %s must be float32%s, got %s" % (n, " or uint8" if n == "weight" else "", t.dtype))
-    if any(t.device != final_shading.device for _, t in named):
-        raise _lib.GcfrError("fit_light_rgb: tensors on one device; got %s" % ", ".join(str(t.device) for _, t in named))
+    tensors = _lib.check_tensors("fit_light_rgb", [("final_shading", final_shading), ("albedo", albedo), ("image", image),
+                                                   ("weight", weight), ("out", out)], weight=(torch.float32, torch.uint8))
     if image_layout not in ("nhwc", "nchw"):
         raise _lib.GcfrError("image_layout must be 'nhwc' or 'nchw'; got %r" % (image_layout,))
-    if final_shading.dim() != 4:
-        raise _lib.GcfrError("final_shading must be (B,L,H,W) -- the many-lights form, with its light axis; got %s"
-                             % (tuple(final_shading.shape),))
-    B, L, H, W = final_shading.shape
-    if B < 1 or H < 1 or W < 1 or not 1 <= L <= MAX_FIT_LIGHTS:
-        raise _lib.GcfrError("final_shading (B,L,H,W) = %s: B, H, W >= 1 and 1 <= L <= %d" % (tuple(final_shading.shape), MAX_FIT_LIGHTS))
+    B, L, H, W = _many_lights(final_shading, MAX_FIT_LIGHTS)
+    of = " for final_shading %s" % (tuple(final_shading.shape),)
     if B > 65535 or H * W >= 2 ** 31 - LIGHT_FIT_CHUNK:
         raise _lib.GcfrError("final_shading (B,L,H,W) = %s: B <= 65535 and H W < 2^31 - %d" % (tuple(final_shading.shape), LIGHT_FIT_CHUNK))
-    if tuple(albedo.shape) != (B, 3, H, W):
-        raise _lib.GcfrError("albedo must be %s for final_shading %s; got %s" % ((B, 3, H, W), tuple(final_shading.shape), tuple(albedo.shape)))
-    want = (B, H, W, 3) if image_layout == "nhwc" else (B, 3, H, W)
-    if tuple(image.shape) != want:
-        raise _lib.GcfrError("image must be %s (image_layout=%r) for final_shading %s; got %s"
-                             % (want, image_layout, tuple(final_shading.shape), tuple(image.shape)))
-    if weight is not None and tuple(weight.shape) not in ((H, W), (1, H, W), (B, H, W)):
-        raise _lib.GcfrError("weight must be (%d,%d,%d), (1,%d,%d) or (%d,%d); got %s" % (B, H, W, H, W, H, W, tuple(weight.shape)))
+    _lib.check_shape("albedo", albedo, (B, 3, H, W), why=of)
+    _lib.check_shape("image", image, (B, H, W, 3) if image_layout == "nhwc" else (B, 3, H, W), why=" (image_layout=%r)" % image_layout + of)
+    if weight is not None:
+        _lib.check_shape("weight", weight, (B, H, W), (1, H, W), (H, W))
     if not (isinstance(ridge, (int, float)) and math.isfinite(ridge) and ridge >= 0.0):
         raise _lib.GcfrError("ridge must be a finite number >= 0; got %r" % (ridge,))
     if isinstance(max_solves, bool) or not isinstance(max_solves, int) or not 0 <= max_solves < 2 ** 31:
         raise _lib.GcfrError("max_solves must be an int >= 0 (0: the default cap, 3 L); got %r" % (max_solves,))
-    if out is not None:
-        rigs = 1 if shared else B
-        if tuple(out.shape) != (rigs, L, 3) or not out.is_contiguous():
-            raise _lib.GcfrError("out must be a contiguous (%d,%d,3) tensor; got %s" % (rigs, L, tuple(out.shape)))
-        if out.requires_grad:
-            raise _lib.GcfrError("out must not require a gradient: it is a buffer the result is written into")
-    _lib.require_device(*[t for _, t in named])
+    _lib.check_out(out, (1 if shared else B, L, 3))
+    _lib.require_device(*tensors)
 
 
 def _fit_weight(weight):
@@ -586,42 +472,16 @@ def _fit_weight(weight):
     return (w[None] if w.dim() == 2 else w).contiguous()
 
 
-def _launch_fit_normal(final, albedo, image, nhwc, weight, gram, rhs):
-    B, L, H, W = final.shape
-    dev = final.device
-    lib = _lib.load()
-    with torch.cuda.device(dev):
-        ws = torch.empty(max(8, int(lib.gcfr_light_fit_workspace_bytes(B, L, H, W))) // 8, dtype=torch.float64, device=dev)
-        _lib.check(lib.gcfr_light_fit_normal(final.data_ptr(), albedo.data_ptr(), image.data_ptr(), 1 if nhwc else 0, _lib.ptr(weight),
-                                             1 if weight is None else weight.shape[0], B, L, H, W, ws.data_ptr(), gram.data_ptr(),
-                                             rhs.data_ptr(), _lib.stream_ptr(dev)), "gcfr_light_fit_normal")
-
-
-def _launch_fit_solve(gram, rhs, ridge, rgb, info):
-    B, _, L, _ = gram.shape
-    dev = gram.device
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().gcfr_light_fit_solve(gram.data_ptr(), rhs.data_ptr(), B, L, float(ridge), rgb.shape[0], rgb.data_ptr(),
-                                                    info.data_ptr(), _lib.stream_ptr(dev)), "gcfr_light_fit_solve")
-
-
-def _launch_fit_solve_nonneg(gram, rhs, ridge, max_solves, rgb, info, solves):
-    B, _, L, _ = gram.shape
-    dev = gram.device
-    with torch.cuda.device(dev):
-        _lib.check(_lib.load().gcfr_light_fit_solve_nonneg(gram.data_ptr(), rhs.data_ptr(), B, L, float(ridge), rgb.shape[0], max_solves,
-                                                           rgb.data_ptr(), info.data_ptr(), solves.data_ptr(), _lib.stream_ptr(dev)),
-                   "gcfr_light_fit_solve_nonneg")
-
-
 def _normal_equations(final_shading, albedo, image, weight, image_layout):
     """light_normal_equations behind its checks"""
-    B, L, _, _ = final_shading.shape
+    B, L, H, W = final_shading.shape
     dev = final_shading.device
     gram = torch.empty((B, 3, L, L), dtype=torch.float64, device=dev)
     rhs = torch.empty((B, 3, L), dtype=torch.float64, device=dev)
-    _launch_fit_normal(final_shading.detach().contiguous(), albedo.detach().contiguous(), image.detach().contiguous(),
-                       image_layout == "nhwc", _fit_weight(weight), gram, rhs)
+    final, alb, img, w = final_shading.detach().contiguous(), albedo.detach().contiguous(), image.detach().contiguous(), _fit_weight(weight)
+    ws = torch.empty(max(8, int(_lib.load().gcfr_light_fit_workspace_bytes(B, L, H, W))) // 8, dtype=torch.float64, device=dev)
+    _lib.launch("gcfr_light_fit_normal", dev, final, alb, img, 1 if image_layout == "nhwc" else 0, w, 1 if w is None else w.shape[0],
+                B, L, H, W, ws, gram, rhs, _lib.STREAM)
     return gram, rhs
 
 
@@ -674,7 +534,7 @@ def fit_light_rgb(final_shading: torch.Tensor, albedo: torch.Tensor, image: torc
     info = torch.empty((rigs, 3), dtype=torch.int32, device=dev)
     if nonnegative:
         solves = torch.empty((rigs, 3), dtype=torch.int32, device=dev)
-        _launch_fit_solve_nonneg(gram, rhs, ridge, max_solves, rgb, info, solves)
+        _lib.launch("gcfr_light_fit_solve_nonneg", dev, gram, rhs, B, L, float(ridge), rigs, max_solves, rgb, info, solves, _lib.STREAM)
         return (rgb, info, solves) if return_info else rgb
-    _launch_fit_solve(gram, rhs, ridge, rgb, info)
+    _lib.launch("gcfr_light_fit_solve", dev, gram, rhs, B, L, float(ridge), rigs, rgb, info, _lib.STREAM)
     return (rgb, info) if return_info else rgb

@@ -51,11 +51,8 @@ class _ImageLossesFunction(torch.autograd.Function):
         ws_bytes = int(L_.gcfr_image_losses_workspace_bytes(B, H, W))
         ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=dev)
         win = _window()
-        with torch.cuda.device(dev):
-            _lib.check(L_.gcfr_image_losses_fwd(rendered.data_ptr(), images.data_ptr(), _lib.ptr(mask), layout, B, H, W,
-                                                ctypes.cast(win, ctypes.c_void_p), data_range, composite.data_ptr(), ssim.data_ptr(),
-                                                sums.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev)),
-                       "gcfr_image_losses_fwd")
+        _lib.launch("gcfr_image_losses_fwd", dev, rendered, images, mask, layout, B, H, W, ctypes.cast(win, ctypes.c_void_p),
+                    data_range, composite, ssim, sums, ws, ws_bytes, _lib.STREAM)
         recon_sq_sum, mask_sum = sums[0].float(), sums[1].float()
         ctx.save_for_backward(rendered, images, mask)
         ctx.layout, ctx.data_range = layout, data_range
@@ -66,17 +63,13 @@ class _ImageLossesFunction(torch.autograd.Function):
     @staticmethod
     def backward(ctx, g_composite, g_recon, _g_mask_sum, g_ssim):
         rendered, images, mask = ctx.saved_tensors
-        L_ = _lib.load()
         B, _, H, W = rendered.shape
         dev = rendered.device
-        ptr = _lib.ptr
         g_composite, g_recon, g_ssim = _lib.f32c(g_composite), _lib.f32c(g_recon), _lib.f32c(g_ssim)
         grad = torch.empty_like(rendered)
         win = _window()
-        with torch.cuda.device(dev):
-            _lib.check(L_.gcfr_image_losses_bwd(rendered.data_ptr(), images.data_ptr(), ptr(mask), ctx.layout, B, H, W,
-                                                ctypes.cast(win, ctypes.c_void_p), ctx.data_range, ptr(g_composite), ptr(g_ssim),
-                                                ptr(g_recon), grad.data_ptr(), _lib.stream_ptr(dev)), "gcfr_image_losses_bwd")
+        _lib.launch("gcfr_image_losses_bwd", dev, rendered, images, mask, ctx.layout, B, H, W, ctypes.cast(win, ctypes.c_void_p),
+                    ctx.data_range, g_composite, g_ssim, g_recon, grad, _lib.STREAM)
         return grad, None, None, None, None
 
 
@@ -119,20 +112,14 @@ class _SupervisedLossesFunction(torch.autograd.Function):
         sums = torch.empty(4, dtype=torch.float64, device=dev)
         ws_bytes = int(L_.gcfr_supervised_losses_workspace_bytes(B, H, W))
         ws = torch.empty(max(ws_bytes // 8, 1), dtype=torch.float64, device=dev)
-        with torch.cuda.device(dev):
-            _lib.check(L_.gcfr_supervised_losses_fwd(depth.data_ptr(), gt_depth.data_ptr(), mask.data_ptr(), albedo.data_ptr(),
-                                                     gt_albedo.data_ptr(), mask_fill.data_ptr(), unit_light.data_ptr(),
-                                                     ambient_values.data_ptr(), lightings.data_ptr(), _lib.ptr(logits),
-                                                     logits.numel() if logits is not None else 0, B, H, W, terms.data_ptr(),
-                                                     sums.data_ptr(), ws.data_ptr(), ws_bytes, _lib.stream_ptr(dev)),
-                       "gcfr_supervised_losses_fwd")
+        _lib.launch("gcfr_supervised_losses_fwd", dev, depth, gt_depth, mask, albedo, gt_albedo, mask_fill, unit_light, ambient_values,
+                    lightings, logits, logits.numel() if logits is not None else 0, B, H, W, terms, sums, ws, ws_bytes, _lib.STREAM)
         ctx.save_for_backward(depth, albedo, unit_light, ambient_values, logits, gt_depth, mask, gt_albedo, mask_fill, lightings, sums)
         return terms
 
     @staticmethod
     def backward(ctx, g_terms):
         depth, albedo, unit_light, ambient_values, logits, gt_depth, mask, gt_albedo, mask_fill, lightings, sums = ctx.saved_tensors
-        L_ = _lib.load()
         B, _, H, W = depth.shape
         dev = depth.device
         g = g_terms.to(torch.float32).contiguous()                 # stays on the device: the kernel reads the five values there
@@ -140,15 +127,10 @@ class _SupervisedLossesFunction(torch.autograd.Function):
         grad_depth, grad_albedo = torch.empty_like(depth), torch.empty_like(albedo)
         grad_unit_light, grad_ambient = torch.empty_like(unit_light), torch.empty_like(ambient_values)
         grad_logits = torch.empty_like(logits) if logits is not None else None
-        with torch.cuda.device(dev):
-            _lib.check(L_.gcfr_supervised_losses_bwd(depth.data_ptr(), gt_depth.data_ptr(), mask.data_ptr(), albedo.data_ptr(),
-                                                     gt_albedo.data_ptr(), mask_fill.data_ptr(), ambient_values.data_ptr(),
-                                                     lightings.data_ptr(), _lib.ptr(logits),
-                                                     logits.numel() if logits is not None else 0, B, H, W, sums.data_ptr(),
-                                                     gp[0], gp[1], gp[2], gp[3], gp[4] if logits is not None else None,
-                                                     grad_depth.data_ptr(), grad_albedo.data_ptr(), grad_unit_light.data_ptr(),
-                                                     grad_ambient.data_ptr(), _lib.ptr(grad_logits), _lib.stream_ptr(dev)),
-                       "gcfr_supervised_losses_bwd")
+        _lib.launch("gcfr_supervised_losses_bwd", dev, depth, gt_depth, mask, albedo, gt_albedo, mask_fill, ambient_values, lightings,
+                    logits, logits.numel() if logits is not None else 0, B, H, W, sums,
+                    gp[0], gp[1], gp[2], gp[3], gp[4] if logits is not None else None,
+                    grad_depth, grad_albedo, grad_unit_light, grad_ambient, grad_logits, _lib.STREAM)
         return grad_depth, grad_albedo, grad_unit_light, grad_ambient, grad_logits, None, None, None, None, None
 
 

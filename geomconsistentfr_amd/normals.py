@@ -24,13 +24,12 @@ class _NormalsFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, depth, fx, fy, cx, cy, z_offset, negate_y):
         B, _, H, W = depth.shape
-        d = depth.detach().to(torch.float32).contiguous()
+        d = _lib.f32c(depth)
         out = torch.empty((B, 3, H, W), dtype=torch.float32, device=d.device)
         from .block import _normals_fwd_args                     # (the one place that spells the entry's argument order)
-        with torch.cuda.device(d.device):
-            _lib.check(_lib.load().gcfr_normals_fwd(*_normals_fwd_args(
-                depth=d.data_ptr(), B=B, H=H, W=W, fx=fx, fy=fy, cx=cx, cy=cy, z_offset=float(z_offset), negate_y=int(negate_y),
-                normals=out.data_ptr(), stream=torch.cuda.current_stream(d.device).cuda_stream)), "gcfr_normals_fwd")
+        _lib.launch("gcfr_normals_fwd", d.device, *_normals_fwd_args(
+            depth=d, B=B, H=H, W=W, fx=fx, fy=fy, cx=cx, cy=cy, z_offset=float(z_offset), negate_y=int(negate_y), normals=out,
+            stream=_lib.STREAM))
         ctx.save_for_backward(d)
         ctx.k = (fx, fy, cx, cy, float(z_offset), int(negate_y))
         return out
@@ -40,12 +39,9 @@ class _NormalsFunction(torch.autograd.Function):
         (d,) = ctx.saved_tensors
         B, _, H, W = d.shape
         fx, fy, cx, cy, z_offset, negate_y = ctx.k
-        g = g.detach().to(torch.float32).contiguous()
+        g = _lib.f32c(g)
         gd = torch.zeros((B, 1, H, W), dtype=torch.float32, device=d.device)
-        with torch.cuda.device(d.device):
-            _lib.check(_lib.load().gcfr_normals_bwd(g.data_ptr(), d.data_ptr(), B, H, W, fx, fy, cx, cy, z_offset,
-                                                    negate_y, gd.data_ptr(),
-                                                    torch.cuda.current_stream(d.device).cuda_stream), "gcfr_normals_bwd")
+        _lib.launch("gcfr_normals_bwd", d.device, g, d, B, H, W, fx, fy, cx, cy, z_offset, negate_y, gd, _lib.STREAM)
         return gd, None, None, None, None, None, None
 
 
@@ -54,9 +50,7 @@ def depth_to_normals(depth: torch.Tensor, camera_matrix: torch.Tensor, negate_y:
     """depth (B,1,H,W), camera_matrix (1|B,3,3) -> unit normals (B,3,H,W), y negated as the reference does
     right after the call (T8:354).  `z_offset` is added to the depth in f32 first (T8:353: +1610).
     Device tensors only (HIP kernels); there is no CPU path."""
-    if not depth.is_cuda:
-        raise _lib.GcfrError("geomconsistentfr_amd has no CPU path: depth must be on a ROCm device "
-                             "(oracle/normals_restatement.py is the host-side specification used by the tests)")
+    _lib.require_device(depth)          # (oracle/normals_restatement.py is the host-side specification used by the tests)
     from .block import camera_scalars                            # host scalars, read once per tensor (no per-call sync)
     k4 = camera_scalars(camera_matrix)
     if k4 is None:

@@ -32,20 +32,32 @@ def inference_images_device(input_images, rendered, mask_u8, albedo=None, depth=
     no L-fold copy of the input; the per-photograph maps (albedo, depth, normals) keep their (B,...) shapes."""
     import torch
     from . import _lib
-    L_ = _lib.load()
-    x = input_images
-    if not x.is_cuda:
-        raise _lib.GcfrError("geomconsistentfr_amd has no CPU path: tensors must be on a ROCm device")
-    f = lambda t: None if t is None else t.detach().to(torch.float32).contiguous()
-    x, rendered = f(x), f(rendered)
+    what, x = "inference_images_device", input_images
+    per_light = [("shadow_mask_weights", shadow_mask_weights), ("final_shading", final_shading)]
+    per_face = [("albedo", albedo), ("surface_normals", surface_normals)]
+    named = [("input_images", x), ("rendered", rendered)] + per_light + per_face + [("depth", depth)]
+    tensors = _lib.check_tensors(what, named, **{n: _lib.FLOATS for n, _ in named})      # (whatever is not f32 is converted below)
+    _lib.check_tensors(what, [("mask_u8", mask_u8)], mask_u8=torch.uint8)                 # (on any device: it is moved to the images')
+    if x.dim() != 4 or x.shape[3] != 3:
+        raise _lib.GcfrError("input_images must be (B,H,W,3); got %s" % (tuple(x.shape),))
     B, H, W, _ = x.shape
     multi = rendered.dim() == 5
     L = rendered.shape[1] if multi else 1
     lead = (B, L) if multi else (B,)
-    if tuple(rendered.shape) != lead + (3, H, W):
-        raise _lib.GcfrError("rendered must be (B,3,H,W) or (B,L,3,H,W) for input images %s; got %s" % (tuple(x.shape), tuple(rendered.shape)))
-    if mask_u8.dtype != torch.uint8:
-        raise _lib.GcfrError("mask_u8 must be the uint8 skin mask (0..255)")
+    of = " for rendered %s" % (tuple(rendered.shape),)
+    _lib.check_shape("rendered", rendered, (B, 3, H, W), (B, L, 3, H, W), why=" for input images %s" % (tuple(x.shape),))
+    for n, t in per_light:              # the kernel indexes these planes at (b L + l) H W, the per-face ones at b
+        if t is not None:
+            _lib.check_shape(n, t, lead + (H, W), why=of)
+    for n, t in per_face:
+        if t is not None:
+            _lib.check_shape(n, t, (B, 3, H, W), why=" (per face, no light axis)" + of)
+    if depth is not None:
+        _lib.check_shape("depth", depth, (B, 1, H, W), (B, H, W), why=of)
+    _lib.check_shape("mask_u8", mask_u8, (H, W), (1, H, W), (B, H, W), why=" (the uint8 skin mask, 0..255)")
+    _lib.require_device(*tensors)
+    f = _lib.f32c
+    x, rendered = f(x), f(rendered)
     m = mask_u8.to(x.device).contiguous().reshape(-1, H, W)
     albedo, shadow_mask_weights, final_shading, surface_normals = f(albedo), f(shadow_mask_weights), f(final_shading), f(surface_normals)
     drange = None
@@ -65,13 +77,9 @@ def inference_images_device(input_images, rendered, mask_u8, albedo=None, depth=
         out["shading"] = u8(*lead, H, W)
     if surface_normals is not None:
         out["surface_normals"] = u8(B, H, W, 3)
-    p = lambda t: None if t is None else t.data_ptr()
-    with torch.cuda.device(x.device):
-        _lib.check(L_.gcfr_inference_images_u8(
-            x.data_ptr(), rendered.data_ptr(), p(albedo), p(depth), p(drange), p(shadow_mask_weights), p(final_shading),
-            p(surface_normals), m.data_ptr(), m.shape[0], B, L, H, W, out["rendered_image"].data_ptr(), p(out.get("shadow_mask")),
-            p(out.get("albedo")), p(out.get("depth")), p(out.get("shading")), p(out.get("surface_normals")), int(bool(mask_f32)),
-            torch.cuda.current_stream(x.device).cuda_stream), "gcfr_inference_images_u8")
+    _lib.launch("gcfr_inference_images_u8", x.device, x, rendered, albedo, depth, drange, shadow_mask_weights, final_shading,
+                surface_normals, m, m.shape[0], B, L, H, W, out["rendered_image"], out.get("shadow_mask"), out.get("albedo"),
+                out.get("depth"), out.get("shading"), out.get("surface_normals"), int(bool(mask_f32)), _lib.STREAM)
     return out
 
 
@@ -80,15 +88,18 @@ def fix_border_artifacts_device(img_u8, face_mask_u8):
     skin mask as stored on disk.  Returns a new (B,H,W,3) uint8 tensor."""
     import torch
     from . import _lib
-    if not img_u8.is_cuda:
-        raise _lib.GcfrError("geomconsistentfr_amd has no CPU path: tensors must be on a ROCm device")
+    what = "fix_border_artifacts_device"
+    _lib.check_tensors(what, [("img_u8", img_u8)], img_u8=torch.uint8)
+    _lib.check_tensors(what, [("face_mask_u8", face_mask_u8)], face_mask_u8=torch.uint8)  # (on any device: it is moved to the images')
+    if img_u8.dim() != 4 or img_u8.shape[3] != 3:
+        raise _lib.GcfrError("img_u8 must be (B,H,W,3); got %s" % (tuple(img_u8.shape),))
+    B, H, W, _ = img_u8.shape
+    _lib.check_shape("face_mask_u8", face_mask_u8, (H, W), (1, H, W), (B, H, W), why=" for img_u8 %s" % (tuple(img_u8.shape),))
+    _lib.require_device(img_u8)
     img = img_u8.contiguous()
-    B, H, W, _ = img.shape
-    mk = face_mask_u8.to(img.device, torch.uint8).contiguous().reshape(-1, H, W)
+    mk = face_mask_u8.to(img.device).contiguous().reshape(-1, H, W)
     out = torch.empty_like(img)
-    with torch.cuda.device(img.device):
-        _lib.check(_lib.load().gcfr_fix_border_u8(img.data_ptr(), mk.data_ptr(), mk.shape[0], B, H, W, out.data_ptr(),
-                                                  torch.cuda.current_stream(img.device).cuda_stream), "gcfr_fix_border_u8")
+    _lib.launch("gcfr_fix_border_u8", img.device, img, mk, mk.shape[0], B, H, W, out, _lib.STREAM)
     return out
 
 
@@ -97,12 +108,12 @@ FULLRES_MAX_LIGHTS = 4096
 
 
 def _check_photographs(photo_u8, scale, what):
-    """-> (B, h, w, s) of uint8 photographs (B, s h, s w, 3) on the device, or GcfrError"""
+    """-> (B, h, w, s) of uint8 photographs (B, s h, s w, 3), or GcfrError (where they live is the caller's last check)"""
     import torch
     from . import _lib
-    if not torch.is_tensor(photo_u8) or photo_u8.dtype != torch.uint8 or photo_u8.dim() != 4 or photo_u8.shape[-1] != 3:
-        raise _lib.GcfrError("%s: photographs must be a uint8 tensor (B,H,W,3); got %s" % (
-            what, (tuple(photo_u8.shape), photo_u8.dtype) if torch.is_tensor(photo_u8) else type(photo_u8).__name__))
+    _lib.check_tensors(what, [("photographs", photo_u8)], photographs=torch.uint8)
+    if photo_u8.dim() != 4 or photo_u8.shape[-1] != 3:
+        raise _lib.GcfrError("%s: photographs must be a uint8 tensor (B,H,W,3); got %s" % (what, tuple(photo_u8.shape)))
     if isinstance(scale, bool) or not isinstance(scale, int) or scale not in FULLRES_SCALES:
         raise _lib.GcfrError("%s: scale must be one of %s; got %r" % (what, FULLRES_SCALES, scale))
     B, H, W, _ = photo_u8.shape
@@ -110,7 +121,6 @@ def _check_photographs(photo_u8, scale, what):
         raise _lib.GcfrError("%s: photographs %s are not (B, scale h, scale w, 3) for scale %d" % (what, tuple(photo_u8.shape), scale))
     if H * W > 0x7fffffff or B * ((H * W + 1023) // 1024) > 0x7fffffff:
         raise _lib.GcfrError("%s: %d photographs of %d x %d pixels do not fit the kernels' 31-bit pixel and chunk counts" % (what, B, H, W))
-    _lib.require_device(photo_u8)
     return B, H // scale, W // scale, scale
 
 
@@ -123,11 +133,10 @@ def ingest_photographs_device(photo_u8, scale):
     import torch
     from . import _lib
     B, h, w, s = _check_photographs(photo_u8, scale, "ingest_photographs_device")
+    _lib.require_device(photo_u8)
     photo = photo_u8.detach().contiguous()
     x_lo = torch.empty((B, h, w, 3), dtype=torch.float32, device=photo.device)
-    with torch.cuda.device(photo.device):
-        _lib.check(_lib.load().gcfr_ingest_photographs_u8(photo.data_ptr(), B, h, w, s, x_lo.data_ptr(), _lib.stream_ptr(photo.device)),
-                   "gcfr_ingest_photographs_u8")
+    _lib.launch("gcfr_ingest_photographs_u8", photo.device, photo, B, h, w, s, x_lo, _lib.STREAM)
     return x_lo
 
 
@@ -147,37 +156,28 @@ def fullres_composites_device(photo_u8, x_lo, rendered, mask_u8, scale, detail_c
     what = "fullres_composites_device"
     B, h, w, s = _check_photographs(photo_u8, scale, what)
     H, W = s * h, s * w
-    if not torch.is_tensor(x_lo) or x_lo.dtype != torch.float32 or tuple(x_lo.shape) != (B, h, w, 3):
-        raise _lib.GcfrError("%s: x_lo must be a float32 tensor (%d,%d,%d,3); got %s" % (
-            what, B, h, w, (tuple(x_lo.shape), x_lo.dtype) if torch.is_tensor(x_lo) else type(x_lo).__name__))
-    if not torch.is_tensor(rendered) or not rendered.is_floating_point() or rendered.dim() not in (4, 5):
-        raise _lib.GcfrError("%s: rendered must be a floating-point tensor (B,3,h,w) or (B,L,3,h,w)" % what)
+    tensors = _lib.check_tensors(what, [("x_lo", x_lo), ("rendered", rendered), ("mask_u8", mask_u8), ("out", out)], one_device=False,
+                                 rendered=_lib.FLOATS, mask_u8=torch.uint8, out=torch.uint8)
+    _lib.check_shape("x_lo", x_lo, (B, h, w, 3))
     multi = rendered.dim() == 5
     L = rendered.shape[1] if multi else 1
     lead = (B, L) if multi else (B,)
-    if tuple(rendered.shape) != lead + (3, h, w) or not 1 <= L <= FULLRES_MAX_LIGHTS:
-        raise _lib.GcfrError("%s: rendered must be (%d,3,%d,%d) or (%d,L,3,%d,%d) with 1 <= L <= %d; got %s" % (
-            what, B, h, w, B, h, w, FULLRES_MAX_LIGHTS, tuple(rendered.shape)))
-    if not torch.is_tensor(mask_u8) or mask_u8.dtype != torch.uint8:
-        raise _lib.GcfrError("%s: mask_u8 must be the uint8 skin mask (0..255) at the network's resolution" % what)
-    if tuple(mask_u8.shape) not in ((h, w), (1, h, w), (B, h, w)):
-        raise _lib.GcfrError("%s: mask_u8 must be (%d,%d), (1,%d,%d) or (%d,%d,%d); got %s" % (what, h, w, h, w, B, h, w, tuple(mask_u8.shape)))
+    _lib.check_shape("rendered", rendered, (B, 3, h, w), (B, L, 3, h, w))
+    if not 1 <= L <= FULLRES_MAX_LIGHTS:
+        raise _lib.GcfrError("%s: rendered %s: 1 <= L <= %d" % (what, tuple(rendered.shape), FULLRES_MAX_LIGHTS))
+    _lib.check_shape("mask_u8", mask_u8, (h, w), (1, h, w), (B, h, w), why=" (the uint8 skin mask at the network's resolution)")
     if not float(detail_clamp) >= 1.0 or not float(floor) > 0.0:
         raise _lib.GcfrError("%s: detail_clamp >= 1 and floor > 0; got %r, %r" % (what, detail_clamp, floor))
-    if out is not None:
-        if not torch.is_tensor(out) or out.dtype != torch.uint8 or tuple(out.shape) != lead + (H, W, 3) or not out.is_contiguous():
-            raise _lib.GcfrError("%s: out must be a contiguous uint8 tensor %s" % (what, lead + (H, W, 3)))
-    _lib.require_device(x_lo, rendered, mask_u8, out)
+    _lib.check_out(out, lead + (H, W, 3))
+    _lib.require_device(photo_u8, *tensors)
     photo, x = photo_u8.detach().contiguous(), x_lo.detach().contiguous()
     ren = rendered.detach().to(torch.float32).contiguous()
     m = mask_u8.contiguous().reshape(-1, h, w)
     if out is not None and out.data_ptr() == photo.data_ptr():
         raise _lib.GcfrError("%s: out must not be the photographs" % what)
     res = torch.empty(lead + (H, W, 3), dtype=torch.uint8, device=photo.device) if out is None else out
-    with torch.cuda.device(photo.device):
-        _lib.check(_lib.load().gcfr_fullres_composites_u8(photo.data_ptr(), x.data_ptr(), ren.data_ptr(), m.data_ptr(), m.shape[0], B, L,
-                                                          h, w, s, float(floor), float(detail_clamp), res.data_ptr(),
-                                                          _lib.stream_ptr(photo.device)), "gcfr_fullres_composites_u8")
+    _lib.launch("gcfr_fullres_composites_u8", photo.device, photo, x, ren, m, m.shape[0], B, L, h, w, s, float(floor),
+                float(detail_clamp), res, _lib.STREAM)
     return res
 
 

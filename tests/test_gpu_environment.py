@@ -53,10 +53,10 @@ def _dev(a, misalign=False):
 
 
 def _gpu_cells(dirs, He, We, min_cos):
-    from geomconsistentfr_amd import lighting
+    from geomconsistentfr_amd import _lib, lighting
     rows, _w, cols = lighting._device_tables(He, We, DEV)
     cell = torch.full((He, We), -7, dtype=torch.int32, device=DEV)
-    lighting._launch_env_cells(rows, cols, _dev(dirs), He, We, min_cos, cell)
+    _lib.launch("gcfr_environment_cells", DEV, rows, cols, _dev(dirs), He, We, dirs.shape[0], float(min_cos), cell, _lib.STREAM)
     return cell.cpu().numpy()
 
 
@@ -186,7 +186,7 @@ def test_negative_radiance_is_not_clamped():
 @pytest.mark.parametrize("E,He,We,L", [(2, 5, 7, 4), (1, 16, 32, 12)])
 def test_misaligned_base_pointers(E, He, We, L):
     """every f32 and i32 tensor 4 bytes past a 16-byte boundary (the f64 table stays 8-byte aligned, as the entries require)"""
-    from geomconsistentfr_amd import lighting
+    from geomconsistentfr_amd import _lib
     env, g_rgb = _inputs(7, E, He, We, L)
     dirs = _directions(L)
     rows, row_w, cols = _tables(He, We)
@@ -194,9 +194,9 @@ def test_misaligned_base_pointers(E, He, We, L):
     rgb = _dev(np.full((E, L, 3), np.nan, np.float32), True)
     g_env = _dev(np.full((E, He, We, 3), np.nan, np.float32), True)
     w_d = _dev(row_w)
-    lighting._launch_env_cells(_dev(rows, True), _dev(cols, True), _dev(dirs, True), He, We, -2.0, cell)
-    lighting._launch_env_fwd(_dev(env, True), w_d, cell, L, rgb)
-    lighting._launch_env_bwd(_dev(g_rgb, True), w_d, cell, g_env)
+    _lib.launch("gcfr_environment_cells", DEV, _dev(rows, True), _dev(cols, True), _dev(dirs, True), He, We, L, -2.0, cell, _lib.STREAM)
+    _lib.launch("gcfr_environment_fwd", DEV, _dev(env, True), E, He, We, w_d, cell, L, rgb, _lib.STREAM)
+    _lib.launch("gcfr_environment_bwd", DEV, _dev(g_rgb, True), w_d, cell, E, He, We, L, g_env, _lib.STREAM)
     got = {"cell": cell.cpu().numpy(), "rgb": rgb.cpu().numpy(), "g_env": g_env.cpu().numpy()}
     _check("misaligned (%d,%d,%d)" % (E, He, We), got, env, dirs, -2.0, g_rgb)
 

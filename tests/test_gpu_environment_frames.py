@@ -22,7 +22,7 @@ def _bits(t):
 
 @pytest.mark.parametrize("E,He,We,L,F", [(1, 5, 7, 4, 1), (2, 5, 7, 4, 3), (1, 16, 32, 12, 5)])
 def test_frames_equal_the_stack_of_single_rotations_and_the_cell_maps_the_restatement(E, He, We, L, F):
-    from geomconsistentfr_amd import environment_lights, environment_lights_frames, lighting
+    from geomconsistentfr_amd import _lib, environment_lights, environment_lights_frames, lighting
     env, _g = _inputs(F + L, E, He, We, L)
     dirs, rots = _directions(L), _rotations(F)
     te, td, tr = _dev(env), _dev(dirs), _dev(rots)
@@ -40,7 +40,7 @@ def test_frames_equal_the_stack_of_single_rotations_and_the_cell_maps_the_restat
     dirs_map = torch.stack([td @ tr[f] for f in range(F)])
     rows_d, _w, cols_d = lighting._device_tables(He, We, DEV)
     cell = torch.full((F, He, We), -7, dtype=torch.int32, device=DEV)
-    lighting._launch_env_cells_frames(rows_d, cols_d, dirs_map, He, We, -2.0, cell)
+    _lib.launch("gcfr_environment_cells_frames", DEV, rows_d, cols_d, dirs_map, F, He, We, L, -2.0, cell, _lib.STREAM)
     rows, row_w, cols = _tables(He, We)
     for f in range(F):
         c = emu.cells(rows, cols, dirs_map[f].cpu().numpy(), -2.0)
@@ -54,7 +54,7 @@ def test_frames_equal_the_stack_of_single_rotations_and_the_cell_maps_the_restat
 
 def test_a_nan_direction_in_one_frame_affects_that_frame_only():
     """the frame's direction sets are given to the launchers directly: a NaN in frame 1's light 2"""
-    from geomconsistentfr_amd import lighting
+    from geomconsistentfr_amd import _lib, lighting
     E, He, We, L, F = 2, 16, 32, 12, 3
     env, _g = _inputs(3, E, He, We, L)
     td, tr = _dev(_directions(L)), _dev(_rotations(F))
@@ -64,8 +64,8 @@ def test_a_nan_direction_in_one_frame_affects_that_frame_only():
     def run(d):
         cell = torch.empty((F, He, We), dtype=torch.int32, device=DEV)
         rgb = torch.empty((E, F, L, 3), dtype=torch.float32, device=DEV)
-        lighting._launch_env_cells_frames(rows_d, cols_d, d, He, We, -2.0, cell)
-        lighting._launch_env_fwd_frames(_dev(env), w_d, cell, L, rgb)
+        _lib.launch("gcfr_environment_cells_frames", DEV, rows_d, cols_d, d, F, He, We, L, -2.0, cell, _lib.STREAM)
+        _lib.launch("gcfr_environment_fwd_frames", DEV, _dev(env), E, He, We, w_d, cell, F, L, rgb, _lib.STREAM)
         return cell.cpu().numpy(), rgb.cpu().numpy()
 
     cell0, rgb0 = run(dirs_map)

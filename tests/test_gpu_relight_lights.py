@@ -269,6 +269,31 @@ def test_two_sessions_in_flight_on_two_streams_do_not_disturb_each_other():
     assert not torch.equal(alone[0], alone[1])
 
 
+@pytest.mark.parametrize("graph", [True, False])
+def test_sessions_leave_the_model_they_share_untouched(graph):
+    """Hoisting is an argument of `forward_lights`, not a flag a session writes on the model and puts back: after construction
+    and a run the model has no `hoist_prepass` of its own (the class default still shows through), and two sessions on ONE model
+    -- a plain one and a rig -- return the eager entries' bytes on the same inputs (fixed head outputs: exactly)."""
+    from geomconsistentfr_amd import inference as inf
+    from geomconsistentfr_amd.relightnet import RelightNetSingleImage
+    heads = _fixed_heads(1, 12)
+    net = _fixed(RelightNetSingleImage, heads)
+    rng = np.random.default_rng(5)
+    images = torch.from_numpy(rng.random((1, H, W, 3), dtype=np.float32)).to(DEV)
+    lights = _lights11()[:3]
+    rgb = rng.random((3, 3), dtype=np.float32)
+    plain = inf.RelightSession(net, 1, heads[3], lights, device=DEV, graph=graph)
+    rig = inf.RelightSession(net, 1, heads[3], lights, device=DEV, graph=graph, light_rgb=rgb)
+    assert (plain.graph is not None) == graph and (rig.graph is not None) == graph
+    got_plain, got_rig = plain.run(images).clone(), rig.run(images).clone()
+    assert "hoist_prepass" not in vars(net) and net.hoist_prepass is True
+    assert torch.equal(got_plain, inf.relight_lights_device(net, images, heads[3], lights, device=DEV))
+    assert torch.equal(got_rig, inf.relight_rig_device(net, images, heads[3], lights, rgb, device=DEV))
+    assert torch.equal(plain.run(images), got_plain)                               # the rig session in between changed nothing
+    assert tuple(got_plain.shape) == (1, 3, H, W, 3) and tuple(got_rig.shape) == (1, H, W, 3) and got_rig.float().std() > 1
+    assert "hoist_prepass" not in vars(net)
+
+
 def test_folded_batchnorm_copy_relights_to_the_same_bytes():
     """inference.fold_batchnorm: the eval-mode BatchNorms folded into the convolutions in front of them (56 elementwise kernels
     per pass fewer).  Network outputs agree to ~1e-5 relative with the two-step evaluation, the composites on >= 99.9 % of the

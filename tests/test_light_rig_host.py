@@ -133,8 +133,7 @@ def test_combine_lights_refuses_malformed_inputs_before_any_launch(monkeypatch):
 
     def reached(*a, **k):
         raise AssertionError("a malformed input reached the launch")
-    monkeypatch.setattr(lighting, "_launch_fwd", reached)
-    monkeypatch.setattr(lighting, "_launch_bwd", reached)
+    monkeypatch.setattr(_lib, "launch", reached)
     monkeypatch.setattr(_lib, "load", reached)
     B, L, H, W = 2, 3, 4, 5
     z = lambda *s, **k: torch.zeros(*s, dtype=k.get("dtype", torch.float32), device=k.get("device", "cpu"))

@@ -58,7 +58,7 @@ def main():
     if not torch.cuda.is_available():
         sys.exit("environment_ab.py needs a GPU (a timing taken anywhere else says nothing)")
     import scenes
-    from geomconsistentfr_amd import build, environment_lights, lighting
+    from geomconsistentfr_amd import _lib, build, environment_lights, lighting
     from geomconsistentfr_amd import inference as inf
     from geomconsistentfr_amd.relightnet import RelightNetLightingTransfer
     dev = torch.device("cuda:0")
@@ -90,7 +90,7 @@ def main():
         dirs = torch.from_numpy(lighting.sphere_directions(L, 0.2)).to(dev)
         rows, row_w, cols = lighting._device_tables(He, We, dev)
         cell = torch.empty((He, We), dtype=torch.int32, device=dev)
-        lighting._launch_env_cells(rows, cols, dirs, He, We, -2.0, cell)
+        _lib.launch("gcfr_environment_cells", dev, rows, cols, dirs, He, We, L, -2.0, cell, _lib.STREAM)
         idx = cell.reshape(-1).to(torch.int64)
         w = row_w.repeat_interleave(We)[None, :, None]                                # (1,T,1) f64
 
