@@ -36,21 +36,14 @@
 // of 16.  Otherwise lane t owns pixels t, t + 256, t + 512, t + 768 and everything moves one element at a time: the same bytes.
 // Bytes per hi-res pixel: 3 read, 3 L written; the low-resolution planes (x_lo 12, mask 1, rendered 12 L per low-res pixel) once
 // from memory.
-#include "gcfr_composite.hpp"
 #include "gcfr_device.hpp"
-#include "gcfr_reduce.hpp"
+#include "gcfr_fullres.hpp"
 
 #include "../../include/gcfr.h"
 
 namespace gcfr {
 
-constexpr int kFullresMaxLights = 4096;        // the image kernel's limit
-
-template <int S>
-constexpr int log2_of() { return S == 1 ? 0 : S == 2 ? 1 : S == 4 ? 2 : 3; }
-// the window of the vector path: pixel k's left tap, and the window's width
-template <int S>
-constexpr int kP0(int k) { return S == 1 ? k : S == 2 ? (k + 1) / 2 : S == 4 ? k / 2 : 0; }
+// the window of the vector path: pixel k's left tap is column kP0<S>(k) (gcfr_fullres.hpp) of a window this wide
 template <int S>
 constexpr int kWin() { return S == 1 ? 5 : S == 2 ? 4 : 3; }
 
@@ -70,24 +63,6 @@ __device__ inline float bilerp(float a00, float a01, float a10, float a11, float
     const float top = a00 + tx * (a01 - a00);
     const float bot = a10 + tx * (a11 - a10);
     return top + ty * (bot - top);
-}
-
-__device__ inline float detail_of(float p, float xl_up, float floor, float lo, float hi)
-{
-    const float xl = xl_up * 255.0f;
-    return fminf(fmaxf(p / fmaxf(xl, floor), lo), hi);
-}
-
-// v of the statement, and the byte where the mask is not zero
-__device__ inline float fullres_value(float p, float m, float d, float r_up)
-{
-    const float r = r_up * 255.0f;
-    return p + m * (r * d - p);
-}
-
-__device__ inline uint8_t fullres_byte(uint8_t photo, float p, float m, float d, float r_up)
-{
-    return m > 0.0f ? quantise_u8((double)fullres_value(p, m, d, r_up)) : photo;
 }
 
 template <int S, bool VEC>
@@ -301,23 +276,6 @@ __global__ __launch_bounds__(kQuadLanes) void ingest_photographs_kernel(const ui
                 xl_b[3u * (size_t)px + c] = (float)((double)acc[c] / den);
         }
     }
-}
-
-inline bool fullres_aligned4(const void *p) { return ((uintptr_t)p & 3u) == 0; }
-inline bool fullres_scale_ok(int32_t s) { return s == 1 || s == 2 || s == 4 || s == 8; }
-
-// (B, h, w, s) -> the hi-res and the low-res pixel counts per face; false where a per-face pixel count or a chunk count does not
-// fit 31 bits
-inline bool fullres_shape(int32_t B, int32_t h, int32_t w, int32_t s, uint32_t &HW, uint32_t &hw)
-{
-    if (B < 1 || h < 1 || w < 1 || !fullres_scale_ok(s))
-        return false;
-    const uint64_t hw64 = (uint64_t)h * (uint64_t)w, HW64 = hw64 * (uint64_t)(s * s);
-    if (hw64 > 0x7fffffffull || HW64 > 0x7fffffffull || (uint64_t)w * (uint64_t)s > 0x7fffffffull ||
-        (uint64_t)B * ((HW64 + kQuadChunk - 1) / kQuadChunk) > 0x7fffffffull)
-        return false;
-    HW = (uint32_t)HW64, hw = (uint32_t)hw64;
-    return true;
 }
 
 template <int S>

@@ -1,0 +1,329 @@
+// Full-resolution relighting, gfx950: the composite of gcfr_fullres.hip with an EDGE-AWARE (joint-bilateral) upsample Up_J in
+// place of the bilinear Up, guided by the photograph itself.  Same operands, layouts and limits as gcfr_fullres_composites_u8,
+// plus `range_sigma` (grey levels).  s is 1, 2, 4 or 8.
+//
+// Arithmetic (-ffp-contract=off: every operation below is one separately rounded IEEE f32 operation unless marked f64; max / min
+// are fmaxf / fminf; the divisions are the correctly rounded f32 division).
+//   Taps        per axis and hi-res index y of a low-resolution axis of n, in integers: u = max(2 y + 1 - s, 0), y0 = u div 2 s,
+//               r = u mod 2 s (Up's u and y0).  The four taps are clamp(y0 - 1 + j, 0, n - 1), j = 0..3, with the integer weights
+//               (2 s - r, 4 s - r, 2 s + r, r) over 4 s: a tent of radius two low-resolution pixels.  The four sum to 2 and each
+//               is exact in f32, sy[j], sx[i]; sy[j] sx[i] is exact.  A tap replicated at a border keeps its own weight.
+//   Weights     once per hi-res pixel P, the same for every light.  p[c] = (float)photo_u8[P, c]; for tap (j, i) at low-resolution
+//               pixel q, g[c] = x_lo[q, c] 255.0f:
+//                 e[c] = p[c] - g[c];  d2 = (e[0] e[0] + e[1] e[1]) + e[2] e[2];  k = 1.0f / (1.0f + d2 inv)
+//                 wt = (sy[j] sx[i]) k;  den = the sum of the 16 wt, row-major (j outer, i inner) from wt[0][0];  rcp = 1.0f / den
+//                 wn = wt rcp
+//               inv = 1.0f / (range_sigma range_sigma) is formed once on the host in f32.  k is a Lorentzian: no transcendental.
+//   Up_J(a)(P)  the sum over the 16 taps, row-major, of wn[j][i] a[tap]: the first product starts the sum, every product and sum
+//               is rounded.  All 16 taps are always read: a tap of weight 0 still carries a NaN.
+//   Composite   gcfr_fullres.hip's with Up_J in all three places and the SAME wn: d = detail_of(p, Up_J(x_lo[..., c])),
+//               m = Up_J((float)mask_u8 / 255.0f), v = fullres_value(p, m, d, Up_J(rendered[b, l, c])),
+//               byte = m > 0 ? quantise_u8((double)v) : photo_u8   (gcfr_fullres.hpp, gcfr_composite.hpp: called, not copied)
+//
+// Work split: gcfr_fullres.hip's.  A workgroup of 256 lanes owns kQuadChunk = 1024 consecutive hi-res pixels of ONE face, four per
+// lane.  ONCE per pixel: the 16 normalised weights (48 guide values, 16 divisions for k and one for rcp), d[3] and m.  PER LIGHT:
+// 3 x 16 products and sums per pixel, the blend and the quantisation -- no division and no branch in the light loop; the `m > 0`
+// select is a byte mask formed once per lane.  The registers allow one wave per SIMD (two at s = 8), so nothing but the lane's own
+// arithmetic covers a load: the NEXT light's windows are requested in front of the current light's arithmetic.
+// VEC (W a multiple of four, photograph and output 4-byte aligned): lane t owns pixels 4 t .. 4 t + 3 of the chunk, all in one row;
+// the photograph's 12 bytes arrive as three dwords and every light's 12 bytes leave as three.  The four pixels share their four tap
+// rows and a WINDOW of kGWin<S> consecutive low-resolution columns, loaded once per lane, plane and row (4 x kGWin loads per plane
+// instead of 64) and clamped to [0, w - 1] when loaded.  The window starts at x0 - 1 of the first pixel; pixel k's first tap is
+// window column kP0<S>(k).  Only at the left border (x = 0 and s > 1, where u was clamped to 0 for the pixels with 2 k + 1 < s)
+// does this differ: at s = 8 all four pixels are clamped and the window simply starts at -1; at s = 2 and 4 the window starts at
+// -2 and the clamped pixels read one window column further right.  Otherwise lane t owns pixels t, t + 256, t + 512, t + 768 and
+// everything moves one element at a time: the same bytes.
+#include "gcfr_device.hpp"
+#include "gcfr_fullres.hpp"
+
+#include "../../include/gcfr.h"
+
+namespace gcfr {
+
+// the window's width: the last pixel's offset plus its four taps
+template <int S>
+constexpr int kGWin() { return kP0<S>(3) + 4; }
+
+// one axis of Up_J for hi-res index i of a low-resolution axis of n: the four taps and their weights, all exact
+template <int S>
+__device__ inline void guided_tap(uint32_t i, uint32_t n, uint32_t (&tap)[4], float (&wgt)[4])
+{
+    const uint32_t u2 = 2u * i + 1u;                                               // (i < 2^31)
+    const uint32_t u = u2 < (uint32_t)S ? 0u : u2 - (uint32_t)S;
+    const int32_t i0 = (int32_t)(u >> (log2_of<S>() + 1));
+    const uint32_t r = u & (2u * S - 1u);
+#pragma unroll
+    for (int j = 0; j < 4; ++j) {
+        const int32_t c = i0 - 1 + j;                                              // (n < 2^31)
+        tap[j] = c < 0 ? 0u : ((uint32_t)c < n - 1u ? (uint32_t)c : n - 1u);
+    }
+    constexpr float q = 1.0f / (float)(4 * S);
+    wgt[0] = (float)(2u * S - r) * q, wgt[1] = (float)(4u * S - r) * q, wgt[2] = (float)(2u * S + r) * q, wgt[3] = (float)r * q;
+}
+
+// the range kernel's weight of one tap
+__device__ inline float guided_range(const float (&p)[3], float x0, float x1, float x2, float inv)
+{
+    const float e0 = p[0] - x0 * 255.0f, e1 = p[1] - x1 * 255.0f, e2 = p[2] - x2 * 255.0f;
+    const float d2 = (e0 * e0 + e1 * e1) + e2 * e2;
+    return 1.0f / (1.0f + d2 * inv);
+}
+
+template <int S, bool VEC>
+__global__ __launch_bounds__(kQuadLanes) void fullres_composites_guided_kernel(
+    const uint8_t *__restrict__ photo, const float *__restrict__ x_lo, const float *__restrict__ rendered,
+    const uint8_t *__restrict__ mask, uint32_t mask_stride, uint32_t L, uint32_t h, uint32_t w, uint32_t W, uint32_t HW,
+    uint32_t chunks, float floor, float lo, float hi, float inv, uint8_t *__restrict__ out)
+{
+    const uint32_t b = blockIdx.x / chunks, ch = blockIdx.x - b * chunks;          // (uniform)
+    const uint32_t q = quad_first<VEC>(ch * (uint32_t)kQuadChunk);
+    const uint32_t hw = h * w;
+    const uint8_t *ph_b = photo + (size_t)b * 3u * HW;
+    const float *xl_b = x_lo + (size_t)b * 3u * hw;                                // (h,w,3)
+    const uint8_t *mk_b = mask + (size_t)b * mask_stride;
+    const float *re_b = rendered + (size_t)b * L * 3u * hw;                        // (L,3,h,w)
+    uint8_t *out_b = out + (size_t)b * L * 3u * HW;                                // (L,H,W,3)
+    if (VEC) {
+        if (q >= HW)                                                               // all four pixels in range or none
+            return;
+        const uint32_t y = q / W, x = q - y * W;
+        uint32_t ty[4], roff[4], unused[4];
+        float sy[4];
+        guided_tap<S>(y, h, ty, sy);
+#pragma unroll
+        for (int j = 0; j < 4; ++j)
+            roff[j] = ty[j] * w;
+        constexpr int NW = kGWin<S>();
+        constexpr bool kShift = S == 2 || S == 4;                                  // clamped pixels beside unclamped ones in a lane
+        const bool left = 2u * x + 1u < (uint32_t)S;                               // x = 0 and s > 1
+        const int32_t cb = left ? (kShift ? -2 : -1) : (int32_t)((2u * x + 1u - (uint32_t)S) >> (log2_of<S>() + 1)) - 1;
+        uint32_t col[NW];
+#pragma unroll
+        for (int i = 0; i < NW; ++i) {
+            const int32_t c = cb + i;
+            col[i] = c < 0 ? 0u : ((uint32_t)c < w - 1u ? (uint32_t)c : w - 1u);
+        }
+        // tap (j, i) of pixel k in a loaded window win[row][column]
+        auto tap_of = [&](const float (&win)[4][NW], int k, int j, int i) {
+            const int c = kP0<S>(k) + i;
+            const float here = win[j][c];
+            if (kShift && 2 * k + 1 < S) {                                         // (compile time)
+                const float right = win[j][c + 1];                                 // two values, not a choice between two addresses
+                return left ? right : here;
+            }
+            return here;
+        };
+        // the photograph's 12 bytes
+        const uint32_t *pw = reinterpret_cast<const uint32_t *>(ph_b + 3u * (size_t)q);
+        const uint32_t w3[3] = {pw[0], pw[1], pw[2]};
+        float p[4][3];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int i = 3 * k + c;
+                p[k][c] = (float)(uint8_t)(w3[i / 4] >> (8 * (i % 4)));
+            }
+        // Up_J of one plane at the lane's four pixels
+        float wn[4][16];
+        auto up4 = [&](const float (&win)[4][NW], float (&v)[4]) {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float acc = wn[k][0] * tap_of(win, k, 0, 0);
+#pragma unroll
+                for (int t = 1; t < 16; ++t)
+                    acc = acc + wn[k][t] * tap_of(win, k, t / 4, t % 4);
+                v[k] = acc;
+            }
+        };
+        // once per pixel: the weights from the guide, then d and m
+        float d[3][4], m[4], v[4];
+        {
+            float xw[3][4][NW];
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int i = 0; i < NW; ++i)
+                        xw[c][j][i] = xl_b[3u * (size_t)(roff[j] + col[i]) + c];
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float sx[4];
+                guided_tap<S>(x + (uint32_t)k, w, unused, sx);
+                float den = 0.0f;
+#pragma unroll
+                for (int t = 0; t < 16; ++t) {
+                    const int j = t / 4, i = t % 4;
+                    const float kr = guided_range(p[k], tap_of(xw[0], k, j, i), tap_of(xw[1], k, j, i), tap_of(xw[2], k, j, i), inv);
+                    wn[k][t] = (sy[j] * sx[i]) * kr;
+                    den = t == 0 ? wn[k][0] : den + wn[k][t];
+                }
+                const float rcp = 1.0f / den;
+#pragma unroll
+                for (int t = 0; t < 16; ++t)
+                    wn[k][t] = wn[k][t] * rcp;
+            }
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                up4(xw[c], v);
+#pragma unroll
+                for (int k = 0; k < 4; ++k)
+                    d[c][k] = detail_of(p[k][c], v[k], floor, lo, hi);
+            }
+            float mw[4][NW];
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+#pragma unroll
+                for (int i = 0; i < NW; ++i)
+                    mw[j][i] = mask_quotient_f32(mk_b[roff[j] + col[i]]);
+            up4(mw, m);
+        }
+        uint32_t inside[3] = {0u, 0u, 0u};                                         // the bytes of the three dwords whose pixel has m > 0
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int i = 3 * k + c;
+                inside[i / 4] |= m[k] > 0.0f ? 0xffu << (8 * (i % 4)) : 0u;
+            }
+        // a light's three windows; the NEXT light's are requested before this light's arithmetic, which then covers their way
+        // from the cache (one trip past the end reloads the last light: in bounds, unused)
+        auto load_light = [&](uint32_t l, float (&dst)[3][4][NW]) {
+            const float *re_l = re_b + (size_t)l * 3u * hw;
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int i = 0; i < NW; ++i)
+                        dst[c][j][i] = re_l[(size_t)c * hw + roff[j] + col[i]];
+        };
+        float cur[3][4][NW], nxt[3][4][NW];
+        load_light(0u, cur);
+        for (uint32_t l = 0; l < L; ++l) {
+            load_light(l + 1u < L ? l + 1u : l, nxt);
+            __builtin_amdgcn_sched_barrier(0);                                     // (the loads stay in front of the arithmetic)
+            uint32_t o[3] = {0u, 0u, 0u};
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                up4(cur[c], v);
+#pragma unroll
+                for (int k = 0; k < 4; ++k) {
+                    const int i = 3 * k + c;
+                    o[i / 4] |= (uint32_t)quantise_u8((double)fullres_value(p[k][c], m[k], d[c][k], v[k])) << (8 * (i % 4));
+                }
+            }
+            uint32_t *ow = reinterpret_cast<uint32_t *>(out_b + 3u * ((size_t)l * HW + q));
+#pragma unroll
+            for (int j = 0; j < 3; ++j)                                            // m > 0 ? the relit byte : the photograph's
+                ow[j] = (o[j] & inside[j]) | (w3[j] & ~inside[j]);
+            __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+#pragma unroll
+                    for (int i = 0; i < NW; ++i)
+                        cur[c][j][i] = nxt[c][j][i];
+        }
+    } else {
+#pragma unroll 1
+        for (int k = 0; k < 4; ++k) {
+            const uint32_t px = quad_pixel<false>(q, k);
+            if (px >= HW)
+                continue;
+            const uint32_t y = px / W, x = px - y * W;
+            uint32_t ty[4], tx[4], tap[16];
+            float sy[4], sx[4], wn[16];
+            guided_tap<S>(y, h, ty, sy);
+            guided_tap<S>(x, w, tx, sx);
+#pragma unroll
+            for (int t = 0; t < 16; ++t)
+                tap[t] = ty[t / 4] * w + tx[t % 4];
+            auto up = [&](auto value_at) {
+                float acc = wn[0] * value_at(tap[0]);
+#pragma unroll
+                for (int t = 1; t < 16; ++t)
+                    acc = acc + wn[t] * value_at(tap[t]);
+                return acc;
+            };
+            uint8_t pb[3];
+            float p[3], d[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                pb[c] = ph_b[3u * (size_t)px + c];
+                p[c] = (float)pb[c];
+            }
+            float den = 0.0f;
+#pragma unroll
+            for (int t = 0; t < 16; ++t) {
+                const float *g = xl_b + 3u * (size_t)tap[t];
+                wn[t] = (sy[t / 4] * sx[t % 4]) * guided_range(p, g[0], g[1], g[2], inv);
+                den = t == 0 ? wn[0] : den + wn[t];
+            }
+            const float rcp = 1.0f / den;
+#pragma unroll
+            for (int t = 0; t < 16; ++t)
+                wn[t] = wn[t] * rcp;
+#pragma unroll
+            for (int c = 0; c < 3; ++c)
+                d[c] = detail_of(p[c], up([&](uint32_t t) { return xl_b[3u * (size_t)t + c]; }), floor, lo, hi);
+            const float m = up([&](uint32_t t) { return mask_quotient_f32(mk_b[t]); });
+            for (uint32_t l = 0; l < L; ++l) {
+                const float *re_l = re_b + (size_t)l * 3u * hw;
+                uint8_t *o = out_b + 3u * ((size_t)l * HW + px);
+#pragma unroll
+                for (int c = 0; c < 3; ++c) {
+                    const float *plane = re_l + (size_t)c * hw;
+                    o[c] = fullres_byte(pb[c], p[c], m, d[c], up([&](uint32_t t) { return plane[t]; }));
+                }
+            }
+        }
+    }
+}
+
+template <int S>
+void launch_composites_guided(bool vec, dim3 grid, hipStream_t st, const uint8_t *photo, const float *x_lo, const float *rendered,
+                              const uint8_t *mask, uint32_t mask_stride, uint32_t L, uint32_t h, uint32_t w, uint32_t HW,
+                              uint32_t chunks, float floor, float lo, float hi, float inv, uint8_t *out)
+{
+    const dim3 block(kQuadLanes);
+    const uint32_t W = w * (uint32_t)S;
+    if (vec)
+        hipLaunchKernelGGL((fullres_composites_guided_kernel<S, true>), grid, block, 0, st, photo, x_lo, rendered, mask, mask_stride, L,
+                           h, w, W, HW, chunks, floor, lo, hi, inv, out);
+    else
+        hipLaunchKernelGGL((fullres_composites_guided_kernel<S, false>), grid, block, 0, st, photo, x_lo, rendered, mask, mask_stride, L,
+                           h, w, W, HW, chunks, floor, lo, hi, inv, out);
+}
+
+}  // namespace gcfr
+
+using namespace gcfr;
+
+extern "C" int gcfr_fullres_composites_guided_u8(const uint8_t *photo_u8, const float *x_lo, const float *rendered,
+                                                 const uint8_t *mask_u8, int32_t mask_batch, int32_t B, int32_t L, int32_t h, int32_t w,
+                                                 int32_t s, float floor, float detail_clamp, float range_sigma, uint8_t *out_u8,
+                                                 void *stream)
+{
+    uint32_t HW, hw;
+    if (!photo_u8 || !x_lo || !rendered || !mask_u8 || !out_u8 || out_u8 == photo_u8 || L < 1 || L > kFullresMaxLights ||
+        !fullres_shape(B, h, w, s, HW, hw) || (mask_batch != 1 && mask_batch != B) || !(detail_clamp >= 1.0f) || !(floor > 0.0f) ||
+        !(range_sigma > 0.0f))
+        return GCFR_ERR_INVALID_ARGUMENT;
+    const uint32_t chunks = (HW + kQuadChunk - 1) / kQuadChunk;
+    const uint32_t mask_stride = mask_batch == 1 ? 0u : hw;
+    const bool vec = ((uint32_t)w * (uint32_t)s) % 4u == 0 && fullres_aligned4(photo_u8) && fullres_aligned4(out_u8);
+    const float lo = 1.0f / detail_clamp;
+    const float inv = 1.0f / (range_sigma * range_sigma);                          // +inf -> 0: the spatial tent alone
+    const dim3 grid((uint32_t)B * chunks);
+    hipStream_t st = (hipStream_t)stream;
+    switch (s) {
+    case 1: launch_composites_guided<1>(vec, grid, st, photo_u8, x_lo, rendered, mask_u8, mask_stride, (uint32_t)L, (uint32_t)h, (uint32_t)w, HW, chunks, floor, lo, detail_clamp, inv, out_u8); break;
+    case 2: launch_composites_guided<2>(vec, grid, st, photo_u8, x_lo, rendered, mask_u8, mask_stride, (uint32_t)L, (uint32_t)h, (uint32_t)w, HW, chunks, floor, lo, detail_clamp, inv, out_u8); break;
+    case 4: launch_composites_guided<4>(vec, grid, st, photo_u8, x_lo, rendered, mask_u8, mask_stride, (uint32_t)L, (uint32_t)h, (uint32_t)w, HW, chunks, floor, lo, detail_clamp, inv, out_u8); break;
+    default: launch_composites_guided<8>(vec, grid, st, photo_u8, x_lo, rendered, mask_u8, mask_stride, (uint32_t)L, (uint32_t)h, (uint32_t)w, HW, chunks, floor, lo, detail_clamp, inv, out_u8); break;
+    }
+    return hipGetLastError() == hipSuccess ? GCFR_OK : GCFR_ERR_LAUNCH;
+}

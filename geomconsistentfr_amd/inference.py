@@ -186,52 +186,55 @@ def _as_photographs(photos_u8, device) -> torch.Tensor:
 @torch.no_grad()
 def relight_lights_fullres_device(model, photos_u8, mask_u8, lights, scale: int, ambient: float = 0.5, focal: float = None,
                                   device="cuda", composite_mask_u8=None, epoch: int = 200, detail_clamp: float = 4.0,
-                                  floor: float = 1.0) -> torch.Tensor:
+                                  floor: float = 1.0, upsample: str = "bilinear", range_sigma: float = 20.0) -> torch.Tensor:
     """`relight_lights_fullres` up to the bytes ON THE DEVICE: (B,L,H,W,3) uint8 tensor, nothing copied back.  `photos_u8` /
     `mask_u8` / `lights` may already be device tensors."""
     photos = _as_photographs(photos_u8, device)
     x = pp.ingest_photographs_device(photos, scale)
     out, cm, _transfer = _lights_pass(model, x, mask_u8, lights, ambient, focal, device, composite_mask_u8, epoch)
-    return pp.fullres_composites_device(photos, x, out[5], cm, scale, detail_clamp, floor)
+    return pp.fullres_composites_device(photos, x, out[5], cm, scale, detail_clamp, floor, upsample=upsample, range_sigma=range_sigma)
 
 
 @torch.no_grad()
 def relight_lights_fullres(model, photos_u8, mask_u8, lights, scale: int, ambient: float = 0.5, focal: float = None, device="cuda",
-                           composite_mask_u8=None, epoch: int = 200, detail_clamp: float = 4.0, floor: float = 1.0) -> np.ndarray:
+                           composite_mask_u8=None, epoch: int = 200, detail_clamp: float = 4.0, floor: float = 1.0,
+                           upsample: str = "bilinear", range_sigma: float = 20.0) -> np.ndarray:
     """`relight_lights` on photographs LARGER than the network: photos_u8 (B, s h, s w, 3) uint8 with `scale` s = 1, 2, 4 or 8 and
     (h, w) the network's resolution -> (B,L, s h, s w, 3) uint8 RGB, every face under every one of `lights` (L,3) at the
     photograph's own size.  Three steps on the device: `postprocess.ingest_photographs_device` (block mean / 255: the network's
     input, without a host-side resize), ONE `forward_lights` pass on it, then ONE `postprocess.fullres_composites_device` launch
     for all L lights (quotient / detail transfer: see there for `detail_clamp` and `floor`).  `mask_u8` (and `composite_mask_u8`,
     as in `relight_lights`) stay at the network's resolution (h,w); the upsampled compositing mask blends the relit face into the
-    photograph, and outside it the photograph's bytes are returned untouched.  `model` / `ambient` / `focal` as in
-    `relight_lights`; there is no border fix at full resolution.  One device-to-host copy of B*L*H*W*3 bytes at the end."""
+    photograph, and outside it the photograph's bytes are returned untouched.  `upsample="guided"` carries the relit image, the
+    quotient and the mask up with the edge-aware joint-bilateral upsample guided by the photograph (`range_sigma` in grey levels,
+    an argument and not a tuned value: see `postprocess.fullres_composites_device`); the default "bilinear" is unchanged.
+    `model` / `ambient` / `focal` as in `relight_lights`; there is no border fix at full resolution.  One device-to-host copy of B*L*H*W*3 bytes at the end."""
     return relight_lights_fullres_device(model, photos_u8, mask_u8, lights, scale, ambient, focal, device, composite_mask_u8, epoch,
-                                         detail_clamp, floor).cpu().numpy()
+                                         detail_clamp, floor, upsample, range_sigma).cpu().numpy()
 
 
 @torch.no_grad()
 def relight_rig_fullres_device(model, photos_u8, mask_u8, lights, light_rgb, scale: int, ambient: float = 0.5, focal: float = None,
                                device="cuda", composite_mask_u8=None, epoch: int = 200, detail_clamp: float = 4.0,
-                               floor: float = 1.0) -> torch.Tensor:
+                               floor: float = 1.0, upsample: str = "bilinear", range_sigma: float = 20.0) -> torch.Tensor:
     """`relight_rig_fullres` up to the bytes ON THE DEVICE: (B,H,W,3) uint8 tensor, nothing copied back."""
     photos = _as_photographs(photos_u8, device)
     x = pp.ingest_photographs_device(photos, scale)
     out, cm, _transfer = _lights_pass(model, x, mask_u8, lights, ambient, focal, device, composite_mask_u8, epoch)
     rendered, _ = combine_lights(out[8], out[0], _as(light_rgb, x.device, single=2).contiguous())
-    return pp.fullres_composites_device(photos, x, rendered, cm, scale, detail_clamp, floor)
+    return pp.fullres_composites_device(photos, x, rendered, cm, scale, detail_clamp, floor, upsample=upsample, range_sigma=range_sigma)
 
 
 @torch.no_grad()
 def relight_rig_fullres(model, photos_u8, mask_u8, lights, light_rgb, scale: int, ambient: float = 0.5, focal: float = None,
                         device="cuda", composite_mask_u8=None, epoch: int = 200, detail_clamp: float = 4.0,
-                        floor: float = 1.0) -> np.ndarray:
+                        floor: float = 1.0, upsample: str = "bilinear", range_sigma: float = 20.0) -> np.ndarray:
     """`relight_rig` on photographs larger than the network: ONE (B, s h, s w, 3) uint8 RGB composite per face under the rig of
     `lights` with colour x weight `light_rgb` (as in `relight_rig`).  `relight_lights_fullres`' three steps with
     `lighting.combine_lights`' `rendered` between the pass and the full-resolution launch (L = 1 there); with one light of colour 1
     the composite equals `relight_lights_fullres(...)[:, 0]`.  One device-to-host copy of B*H*W*3 bytes at the end."""
     return relight_rig_fullres_device(model, photos_u8, mask_u8, lights, light_rgb, scale, ambient, focal, device, composite_mask_u8,
-                                      epoch, detail_clamp, floor).cpu().numpy()
+                                      epoch, detail_clamp, floor, upsample, range_sigma).cpu().numpy()
 
 
 def _rig_frames(x, out, cm, light_rgb_frames, transfer: bool, fix_border: bool) -> torch.Tensor:

@@ -140,7 +140,11 @@ def ingest_photographs_device(photo_u8, scale):
     return x_lo
 
 
-def fullres_composites_device(photo_u8, x_lo, rendered, mask_u8, scale, detail_clamp=4.0, floor=1.0, out=None):
+FULLRES_UPSAMPLES = ("bilinear", "guided")
+
+
+def fullres_composites_device(photo_u8, x_lo, rendered, mask_u8, scale, detail_clamp=4.0, floor=1.0, out=None, upsample="bilinear",
+                              range_sigma=20.0):
     """The relit low-resolution `rendered` of ONE pass carried back onto the photographs' own pixels, as uint8 on the device:
     photo_u8 (B, s h, s w, 3) uint8; x_lo (B,h,w,3) f32, the network's input (`ingest_photographs_device`); rendered (B,L,3,h,w)
     -> (B,L,H,W,3), or (B,3,h,w) -> (B,H,W,3); mask_u8 (1|B,h,w) or (h,w) uint8, the compositing mask AT THE NETWORK'S RESOLUTION
@@ -149,11 +153,21 @@ def fullres_composites_device(photo_u8, x_lo, rendered, mask_u8, scale, detail_c
     bilinearly upsampled relit image, and the upsampled mask m BLENDS it with the photograph, v = p + m (255 Up(rendered) d - p);
     where m is 0 the photograph's byte is kept, whatever `rendered` holds there.  `floor` is in grey levels.  ONE launch for all L
     lights: the photograph, x_lo and the mask are read once per pixel.  `rendered` is the only operand that may be non-f32 on
-    entry.  `out`: a contiguous uint8 buffer of the result's shape that is written and returned (not the photographs).  NOT
-    DIFFERENTIABLE.  No host synchronisation; a malformed input raises GcfrError before anything is loaded or launched."""
+    entry.  `out`: a contiguous uint8 buffer of the result's shape that is written and returned (not the photographs).
+    `upsample`: "bilinear" (the default) is the launch described above; "guided" replaces Up in all three places by the
+    EDGE-AWARE joint-bilateral upsample of csrc/gcfr_fullres_guided.hip (include/gcfr.h states it): a 4 x 4 tent of low-resolution
+    taps whose weights fall off with the squared distance, in grey levels, between the photograph's pixel and 255 x_lo at the tap,
+    k = 1 / (1 + d2 / range_sigma^2), so that neither the relighting gain nor the mask crosses an edge the network's resolution
+    does not see.  `range_sigma` > 0 (grey levels; +inf: the spatial tent alone) is used by "guided" only; its default of 20 is an
+    argument, NOT a tuned value.  NOT DIFFERENTIABLE.  No host synchronisation; a malformed input raises GcfrError before anything
+    is loaded or launched."""
     import torch
     from . import _lib
     what = "fullres_composites_device"
+    if upsample not in FULLRES_UPSAMPLES:
+        raise _lib.GcfrError("%s: upsample must be one of %s; got %r" % (what, FULLRES_UPSAMPLES, upsample))
+    if isinstance(range_sigma, bool) or not isinstance(range_sigma, (int, float)) or not float(range_sigma) > 0.0:
+        raise _lib.GcfrError("%s: range_sigma > 0 (grey levels); got %r" % (what, range_sigma))
     B, h, w, s = _check_photographs(photo_u8, scale, what)
     H, W = s * h, s * w
     tensors = _lib.check_tensors(what, [("x_lo", x_lo), ("rendered", rendered), ("mask_u8", mask_u8), ("out", out)], one_device=False,
@@ -176,6 +190,10 @@ def fullres_composites_device(photo_u8, x_lo, rendered, mask_u8, scale, detail_c
     if out is not None and out.data_ptr() == photo.data_ptr():
         raise _lib.GcfrError("%s: out must not be the photographs" % what)
     res = torch.empty(lead + (H, W, 3), dtype=torch.uint8, device=photo.device) if out is None else out
+    if upsample == "guided":
+        _lib.launch("gcfr_fullres_composites_guided_u8", photo.device, photo, x, ren, m, m.shape[0], B, L, h, w, s, float(floor),
+                    float(detail_clamp), float(range_sigma), res, _lib.STREAM)
+        return res
     _lib.launch("gcfr_fullres_composites_u8", photo.device, photo, x, ren, m, m.shape[0], B, L, h, w, s, float(floor),
                 float(detail_clamp), res, _lib.STREAM)
     return res

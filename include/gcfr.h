@@ -652,6 +652,41 @@ int gcfr_fullres_composites_u8(const uint8_t *photo_u8, const float *x_lo, const
                                int32_t mask_batch, int32_t B, int32_t L, int32_t h, int32_t w, int32_t s, float floor,
                                float detail_clamp, uint8_t *out_u8, void *stream);
 
+/*
+ * The same composite with an EDGE-AWARE (joint-bilateral) upsample Up_J, guided by the photograph, in place of the bilinear Up
+ * (csrc/gcfr_fullres_guided.hip): the relighting gain no longer mixes the two sides of an edge the network's resolution does not
+ * see, and the mask no longer leaks across it.  Operands, layouts and limits are gcfr_fullres_composites_u8's; `range_sigma` is in
+ * grey levels.  Every operation is one separately rounded IEEE f32 operation; the divisions are correctly rounded.
+ *   Taps, per axis and hi-res index y of a low-resolution axis of n, in integers: u = max(2 y + 1 - s, 0), y0 = u div 2 s,
+ *            r = u mod 2 s (Up's u and y0).  The four taps are clamp(y0 - 1 + j, 0, n - 1), j = 0..3, with the integer weights
+ *            (2 s - r, 4 s - r, 2 s + r, r) over 4 s: a tent of radius two low-resolution pixels.  The four sum to 2, each is exact
+ *            in f32 (sy[j], sx[i]) and so is sy[j] sx[i].  A tap replicated at a border keeps its own weight.
+ *   Weights, once per hi-res pixel P, the same for every light.  p[c] = (float)photo_u8[P, c]; for tap (j, i) at low-resolution
+ *            pixel q, g[c] = x_lo[q, c] 255.0f:
+ *              e[c] = p[c] - g[c];  d2 = (e[0] e[0] + e[1] e[1]) + e[2] e[2];  k = 1.0f / (1.0f + d2 inv)
+ *              wt = (sy[j] sx[i]) k;  den = the sum of the 16 wt, row-major (j outer, i inner), starting from wt[0][0]
+ *              rcp = 1.0f / den;  wn = wt rcp
+ *            with inv = 1.0f / (range_sigma range_sigma) formed once on the host in f32.  k is a Lorentzian range kernel: no
+ *            transcendental.  range_sigma = +inf gives inv = 0 and k = 1: the spatial tent alone, den == 4 exactly.
+ *   Up_J(a)(P) = the sum over the 16 taps, row-major, of wn[j][i] a[tap]: the first product starts the sum and every product and
+ *            sum is rounded.  All 16 taps are always read (a tap of weight 0 still carries a NaN into its pixel).
+ *   Composite: the one above with Up_J in all three places and the SAME wn for each:
+ *            xl = Up_J(x_lo[..., c]) 255.0f;  d = min(max(p / max(xl, floor), 1.0f / detail_clamp), detail_clamp)
+ *            m = Up_J((float)mask_u8 / 255.0f);  r = Up_J(rendered[b,l,c]) 255.0f;  v = p + m (r d - p)
+ *            byte = m > 0 ? saturate(rint((double)v)) : photo_u8
+ *   Consequences: rendered == x_lo with no pixel clamped (d strictly inside its bounds, xl >= floor) returns the photograph in
+ *   every byte.  A NaN in x_lo makes m a NaN at the pixels it reaches (it is in their wn), so they keep the photograph's byte.  A
+ *   NaN in `rendered` alone gives byte 0 where m > 0.
+ * Refusals: gcfr_fullres_composites_u8's, and range_sigma <= 0 or a NaN; GCFR_ERR_INVALID_ARGUMENT before the launch.  One launch;
+ * allocates nothing, never synchronises, may be captured into a graph.  Bit-equal to the numpy restatement
+ * (tests/fullres_guided_emulation.py).  The weights, d and m are formed once per pixel; per light a pixel costs 3 x 16 products and
+ * sums, the blend and the quantisation.  Three dwords per four pixels on the same conditions as above; one element at a time
+ * otherwise (same results).
+ */
+int gcfr_fullres_composites_guided_u8(const uint8_t *photo_u8, const float *x_lo, const float *rendered, const uint8_t *mask_u8,
+                                      int32_t mask_batch, int32_t B, int32_t L, int32_t h, int32_t w, int32_t s, float floor,
+                                      float detail_clamp, float range_sigma, uint8_t *out_u8, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Environment-map lighting: a lat-long radiance map integrated into the `rgb` (colour x weight per light) of the light-rig stage
  * above (csrc/gcfr_environment.hip).  Every texel belongs to the light direction nearest to it; a light's rgb is the
