@@ -237,6 +237,76 @@ def relight_rig_fullres(model, photos_u8, mask_u8, lights, light_rgb, scale: int
                                       epoch, detail_clamp, floor, upsample, range_sigma).cpu().numpy()
 
 
+def _network_size(mask_u8):
+    """(h, w) of the network from the mask that goes with it: (h,w) or (1,h,w) uint8"""
+    shape = tuple(mask_u8.shape) if torch.is_tensor(mask_u8) else np.asarray(mask_u8).shape
+    if len(shape) not in (2, 3) or (len(shape) == 3 and shape[0] != 1) or min(shape) < 1:
+        raise GcfrError("mask_u8 must be (h,w) or (1,h,w) at the network's resolution; got %s" % (shape,))
+    return int(shape[-2]), int(shape[-1])
+
+
+def _check_host_boxes(boxes):
+    if torch.is_tensor(boxes) and boxes.is_cuda:
+        raise GcfrError("boxes are HOST integers (x0, y0, bw, bh); got a tensor on %s" % boxes.device)
+
+
+@torch.no_grad()
+def relight_lights_in_photograph_device(model, photos_u8, boxes, mask_u8, lights, ambient: float = 0.5, focal: float = None,
+                                        device="cuda", composite_mask_u8=None, epoch: int = 200, detail_clamp: float = 4.0,
+                                        floor: float = 1.0, paste: bool = True) -> torch.Tensor:
+    """`relight_lights_in_photograph` up to the bytes ON THE DEVICE: (B,L,Hp,Wp,3) uint8 tensor (`paste=False`: (B,L,bh,bw,3)),
+    nothing copied back.  `photos_u8` / `mask_u8` / `lights` may already be device tensors; `boxes` stay on the host."""
+    _check_host_boxes(boxes)
+    photos = _as_photographs(photos_u8, device)
+    x = pp.ingest_box_device(photos, boxes, _network_size(mask_u8))
+    out, cm, _transfer = _lights_pass(model, x, mask_u8, lights, ambient, focal, device, composite_mask_u8, epoch)
+    return pp.fullres_box_composites_device(photos, boxes, x, out[5], cm, detail_clamp, floor, paste=paste)
+
+
+@torch.no_grad()
+def relight_lights_in_photograph(model, photos_u8, boxes, mask_u8, lights, ambient: float = 0.5, focal: float = None, device="cuda",
+                                 composite_mask_u8=None, epoch: int = 200, detail_clamp: float = 4.0, floor: float = 1.0,
+                                 paste: bool = True) -> np.ndarray:
+    """`relight_lights` on a FACE BOX inside a larger photograph: photos_u8 (B,Hp,Wp,3) uint8 of any size, `boxes` host integers
+    (x0, y0, bw, bh) in photograph pixels -- (4,) for every face or (B,4), whatever a detector reports, never smaller than the
+    network's input -> (B,L,Hp,Wp,3) uint8 RGB: every photograph under every one of `lights` (L,3), relit inside its box and
+    untouched outside it (`paste=False`: the boxes alone, (B,L,bh,bw,3), all of one size).  Three steps on the device:
+    `postprocess.ingest_box_device` (the exact area mean of the box: the network's input, without a host-side crop and resize),
+    ONE `forward_lights` pass on it, then ONE `postprocess.fullres_box_composites_device` launch for all L lights.  The network's
+    size (h, w) is `mask_u8`'s; `mask_u8` and `composite_mask_u8` are in the box's frame.  `model` / `ambient` / `focal` as in
+    `relight_lights`; `detail_clamp` / `floor` as in `relight_lights_fullres`, whose bytes these are when the box is the whole
+    photograph at 1, 2, 4 or 8 times the network's side.  The edge-aware upsample is not available over a box.  One
+    device-to-host copy of the result at the end."""
+    return relight_lights_in_photograph_device(model, photos_u8, boxes, mask_u8, lights, ambient, focal, device, composite_mask_u8,
+                                               epoch, detail_clamp, floor, paste).cpu().numpy()
+
+
+@torch.no_grad()
+def relight_rig_in_photograph_device(model, photos_u8, boxes, mask_u8, lights, light_rgb, ambient: float = 0.5, focal: float = None,
+                                     device="cuda", composite_mask_u8=None, epoch: int = 200, detail_clamp: float = 4.0,
+                                     floor: float = 1.0, paste: bool = True) -> torch.Tensor:
+    """`relight_rig_in_photograph` up to the bytes ON THE DEVICE: (B,Hp,Wp,3) uint8 tensor (`paste=False`: (B,bh,bw,3)), nothing
+    copied back."""
+    _check_host_boxes(boxes)
+    photos = _as_photographs(photos_u8, device)
+    x = pp.ingest_box_device(photos, boxes, _network_size(mask_u8))
+    out, cm, _transfer = _lights_pass(model, x, mask_u8, lights, ambient, focal, device, composite_mask_u8, epoch)
+    rendered, _ = combine_lights(out[8], out[0], _as(light_rgb, x.device, single=2).contiguous())
+    return pp.fullres_box_composites_device(photos, boxes, x, rendered, cm, detail_clamp, floor, paste=paste)
+
+
+@torch.no_grad()
+def relight_rig_in_photograph(model, photos_u8, boxes, mask_u8, lights, light_rgb, ambient: float = 0.5, focal: float = None,
+                              device="cuda", composite_mask_u8=None, epoch: int = 200, detail_clamp: float = 4.0, floor: float = 1.0,
+                              paste: bool = True) -> np.ndarray:
+    """`relight_rig` on a face box inside a larger photograph: ONE (B,Hp,Wp,3) uint8 RGB composite per photograph under the rig of
+    `lights` with colour x weight `light_rgb` (as in `relight_rig`), relit inside its box.  `relight_lights_in_photograph`'s
+    three steps with `lighting.combine_lights`' `rendered` between the pass and the box launch (L = 1 there); with one light of
+    colour 1 the composite equals `relight_lights_in_photograph(...)[:, 0]`.  One device-to-host copy at the end."""
+    return relight_rig_in_photograph_device(model, photos_u8, boxes, mask_u8, lights, light_rgb, ambient, focal, device,
+                                            composite_mask_u8, epoch, detail_clamp, floor, paste).cpu().numpy()
+
+
 def _rig_frames(x, out, cm, light_rgb_frames, transfer: bool, fix_border: bool) -> torch.Tensor:
     """`forward_lights`' tuple -> (B,F,H,W,3) uint8: ONE rig-frames launch on its albedo (out[0]) and final shading (out[8]), and
     the optional border fix on the (B F,H,W,3) view"""

@@ -9,6 +9,9 @@ Device path (HIP kernels of csrc/gcfr_postprocess.hip, no CPU fallback): `infere
   ingest_photographs_device     the uint8 photograph at 1, 2, 4 or 8 times the network's side -> the network's f32 input
                                 (S1:515/580 without the host-side cv2.resize), csrc/gcfr_fullres.hip
   fullres_composites_device     the relit low-resolution images carried back onto the photograph's own pixels, uint8
+  ingest_box_device             a face box of any size and position inside a larger photograph -> the network's f32 input,
+                                csrc/gcfr_fullres_box.hip
+  fullres_box_composites_device the relit images carried back onto the box's pixels: the photograph relit inside the box, uint8
 
 Host side: the on-disk formats of load_data() (T8:545-556).  The numpy statements of the script lines these kernels
 implement live in oracle/postprocess_statements.py (test infrastructure, pinned to the reference's own main() by
@@ -196,6 +199,121 @@ def fullres_composites_device(photo_u8, x_lo, rendered, mask_u8, scale, detail_c
         return res
     _lib.launch("gcfr_fullres_composites_u8", photo.device, photo, x, ren, m, m.shape[0], B, L, h, w, s, float(floor),
                 float(detail_clamp), res, _lib.STREAM)
+    return res
+
+
+def _check_boxes(boxes, photo_u8, h, w, what, same_size=False):
+    """-> a contiguous (B,4) int32 numpy array of HOST boxes (x0, y0, bw, bh) that satisfy include/gcfr.h's box rules for the uint8
+    photographs (B,Hp,Wp,3) and a network of (h, w), or GcfrError.  `boxes`: (4,) broadcast over the faces or (B,4); a list, a numpy
+    array or a CPU tensor of integers."""
+    import torch
+    from . import _lib
+    _lib.check_tensors(what, [("photographs", photo_u8)], photographs=torch.uint8)
+    if photo_u8.dim() != 4 or photo_u8.shape[-1] != 3 or min(photo_u8.shape) < 1:
+        raise _lib.GcfrError("%s: photographs must be a uint8 tensor (B,Hp,Wp,3); got %s" % (what, tuple(photo_u8.shape)))
+    B, Hp, Wp, _ = photo_u8.shape
+    if Hp * Wp > 0x7fffffff or B * ((Hp * Wp + 1023) // 1024) > 0x7fffffff:
+        raise _lib.GcfrError("%s: %d photographs of %d x %d pixels do not fit the kernels' 31-bit pixel and chunk counts" % (what, B, Hp, Wp))
+    if any(isinstance(n, bool) or not isinstance(n, int) or n < 1 for n in (h, w)):
+        raise _lib.GcfrError("%s: the network's size (h, w) must be positive integers; got %r" % (what, (h, w)))
+    if torch.is_tensor(boxes):
+        if boxes.is_cuda:
+            raise _lib.GcfrError("%s: boxes are HOST integers (the entry bakes them into its launches); got a tensor on %s" % (what, boxes.device))
+        boxes = boxes.detach().numpy()
+    try:
+        a = np.asarray(boxes)
+    except Exception as e:
+        raise _lib.GcfrError("%s: boxes must be integers (4,) or (B,4): %s" % (what, e))
+    if a.dtype.kind not in "iu":
+        raise _lib.GcfrError("%s: boxes must be integers, got %s" % (what, a.dtype))
+    if a.shape not in ((4,), (B, 4)):
+        raise _lib.GcfrError("%s: boxes must be (4,) or (%d,4) (x0, y0, bw, bh); got %s" % (what, B, a.shape))
+    a = np.broadcast_to(a.astype(np.int64), (B, 4))
+    for b, (x0, y0, bw, bh) in enumerate(a.tolist()):
+        if x0 < 0 or y0 < 0 or x0 + bw > Wp or y0 + bh > Hp:
+            raise _lib.GcfrError("%s: box %d (x0 %d, y0 %d, bw %d, bh %d) does not lie inside the %d x %d photograph" % (what, b, x0, y0, bw, bh, Wp, Hp))
+        if bw < w or bh < h:
+            raise _lib.GcfrError("%s: box %d (%d x %d) is smaller than the network's input (%d x %d)" % (what, b, bw, bh, w, h))
+        if 2 * bh * h > 0x7fffffff or 2 * bw * w > 0x7fffffff:
+            raise _lib.GcfrError("%s: box %d: 2 bh h and 2 bw w must fit 31 bits" % (what, b))
+        if same_size and (bw, bh) != (int(a[0, 2]), int(a[0, 3])):
+            raise _lib.GcfrError("%s: with paste=False all boxes share one (bw, bh); box %d is %d x %d, box 0 is %d x %d"
+                                 % (what, b, bw, bh, int(a[0, 2]), int(a[0, 3])))
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def _host_pointer(a):
+    """a contiguous numpy array's address for a HOST pointer parameter; the caller keeps `a` alive over the call"""
+    import ctypes
+    return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def ingest_box_device(photo_u8, boxes, size):
+    """The network's input from a FACE BOX inside each photograph, on the device: photo_u8 (B,Hp,Wp,3) uint8 of any size, `boxes`
+    host integers (x0, y0, bw, bh) in photograph pixels -- (4,) for every face or (B,4); a list, a numpy array or a CPU tensor --
+    and `size` the network's (h, w) (an int: square) -> (B,h,w,3) f32 in [0,1].  The exact area mean of the box over each
+    low-resolution cell, over 255 (integer overlap weights, a 64-bit sum, one f64 division, one rounding to f32: include/gcfr.h
+    states it; csrc/gcfr_fullres_box.hip).  bw >= w and bh >= h; the two ratios are independent and need not be integers.  With
+    the box the whole photograph at 1, 2, 4 or 8 times the network's side these are `ingest_photographs_device`'s bits.  One
+    launch per 32 faces, no host synchronisation; a malformed input raises GcfrError before anything is loaded or launched."""
+    import torch
+    from . import _lib
+    what = "ingest_box_device"
+    h, w = (size, size) if isinstance(size, int) else (tuple(size) if isinstance(size, (tuple, list)) and len(size) == 2 else (None, None))
+    bx = _check_boxes(boxes, photo_u8, h, w, what)
+    _lib.require_device(photo_u8)
+    photo = photo_u8.detach().contiguous()
+    B, Hp, Wp, _ = photo.shape
+    x_lo = torch.empty((B, h, w, 3), dtype=torch.float32, device=photo.device)
+    _lib.launch("gcfr_ingest_box_u8", photo.device, photo, B, Hp, Wp, _host_pointer(bx), h, w, x_lo, _lib.STREAM)
+    return x_lo
+
+
+def fullres_box_composites_device(photo_u8, boxes, x_lo, rendered, mask_u8, detail_clamp=4.0, floor=1.0, paste=True, out=None):
+    """`fullres_composites_device` for a FACE BOX inside each photograph: photo_u8 (B,Hp,Wp,3) uint8 of any size; `boxes` host
+    integers (x0, y0, bw, bh) as in `ingest_box_device`; x_lo (B,h,w,3) f32, the network's input (`ingest_box_device`); rendered
+    (B,L,3,h,w) or (B,3,h,w); mask_u8 (1|B,h,w) or (h,w) uint8, the compositing mask at the network's resolution IN THE BOX'S
+    FRAME.  `paste=True` -> (B,L,Hp,Wp,3) (or (B,Hp,Wp,3)): the photograph, relit inside the box and untouched outside it;
+    `paste=False` -> (B,L,bh,bw,3): the box alone, all faces then sharing one (bw, bh).  Inside the box the quotient / detail
+    transfer of `fullres_composites_device` with the bilinear Up taken over the box (include/gcfr.h states every operation); with
+    the box the whole photograph at 1, 2, 4 or 8 times the network's side, that entry's bytes.  ONE launch per 32 faces for all L
+    lights; the boxes travel in the launch's arguments, nothing is uploaded.  `rendered` is the only operand that may be non-f32
+    on entry.  `out`: a contiguous uint8 buffer of the result's shape that is written and returned; it must not overlap the
+    photographs.  NOT DIFFERENTIABLE.  No host synchronisation; a malformed input raises GcfrError before anything is loaded or
+    launched."""
+    import torch
+    from . import _lib
+    what = "fullres_box_composites_device"
+    if not isinstance(paste, (bool, int)) or paste not in (0, 1):
+        raise _lib.GcfrError("%s: paste must be True or False; got %r" % (what, paste))
+    tensors = _lib.check_tensors(what, [("x_lo", x_lo), ("rendered", rendered), ("mask_u8", mask_u8), ("out", out)], one_device=False,
+                                 rendered=_lib.FLOATS, mask_u8=torch.uint8, out=torch.uint8)
+    if x_lo.dim() != 4 or x_lo.shape[-1] != 3 or min(x_lo.shape) < 1:
+        raise _lib.GcfrError("%s: x_lo must be (B,h,w,3); got %s" % (what, tuple(x_lo.shape)))
+    h, w = int(x_lo.shape[1]), int(x_lo.shape[2])
+    bx = _check_boxes(boxes, photo_u8, h, w, what, same_size=not paste)
+    B, Hp, Wp, _ = photo_u8.shape
+    _lib.check_shape("x_lo", x_lo, (B, h, w, 3))
+    multi = rendered.dim() == 5
+    L = rendered.shape[1] if multi else 1
+    lead = (B, L) if multi else (B,)
+    _lib.check_shape("rendered", rendered, (B, 3, h, w), (B, L, 3, h, w))
+    if not 1 <= L <= FULLRES_MAX_LIGHTS:
+        raise _lib.GcfrError("%s: rendered %s: 1 <= L <= %d" % (what, tuple(rendered.shape), FULLRES_MAX_LIGHTS))
+    _lib.check_shape("mask_u8", mask_u8, (h, w), (1, h, w), (B, h, w), why=" (the uint8 skin mask at the network's resolution, in the box's frame)")
+    if not float(detail_clamp) >= 1.0 or not float(floor) > 0.0:
+        raise _lib.GcfrError("%s: detail_clamp >= 1 and floor > 0; got %r, %r" % (what, detail_clamp, floor))
+    window = (Hp, Wp) if paste else (int(bx[0, 3]), int(bx[0, 2]))
+    _lib.check_out(out, lead + window + (3,))
+    _lib.require_device(photo_u8, *tensors)
+    photo, x = photo_u8.detach().contiguous(), x_lo.detach().contiguous()
+    ren = rendered.detach().to(torch.float32).contiguous()
+    m = mask_u8.contiguous().reshape(-1, h, w)
+    if out is not None and out.data_ptr() < photo.data_ptr() + photo.numel() and photo.data_ptr() < out.data_ptr() + out.numel():
+        raise _lib.GcfrError("%s: out must not overlap the photographs" % what)
+    res = torch.empty(lead + window + (3,), dtype=torch.uint8, device=photo.device) if out is None else out
+    _lib.launch("gcfr_fullres_composites_box_u8", photo.device, photo, x, ren, m, m.shape[0], B, L, Hp, Wp, _host_pointer(bx), h, w,
+                int(bool(paste)), float(floor), float(detail_clamp), res, _lib.STREAM)
     return res
 
 

@@ -687,6 +687,50 @@ int gcfr_fullres_composites_guided_u8(const uint8_t *photo_u8, const float *x_lo
                                       int32_t mask_batch, int32_t B, int32_t L, int32_t h, int32_t w, int32_t s, float floor,
                                       float detail_clamp, float range_sigma, uint8_t *out_u8, void *stream);
 
+/*
+ * The same two ends for a FACE BOX inside a larger photograph (csrc/gcfr_fullres_box.hip): a box of any integer size and position
+ * in a photograph of any size goes in; the photograph, relit inside the box and untouched outside it, comes out.  A strict
+ * generalisation of the two entries at the top of this section: with the box the whole photograph and bh = s h, bw = s w,
+ * s in {1, 2, 4, 8}, both return those entries' bits.  All arrays contiguous:
+ *   photo_u8   (B,Hp,Wp,3) u8               the photographs, RGB, HWC
+ *   boxes      (B,4) int32, HOST            one box (x0, y0, bw, bh) per face, in photograph pixels
+ *   x_lo       (B,h,w,3) f32                the network's input: what gcfr_ingest_box_u8 writes
+ *   rendered   (B,L,3,h,w) f32              the relit images of ONE many-lights pass
+ *   mask_u8    (mask_batch,h,w) u8          the compositing mask at the network's resolution, IN THE BOX'S FRAME; mask_batch = B or 1
+ *   out_u8     paste = 1: (B,L,Hp,Wp,3) u8 out, the photograph with the box relit
+ *              paste = 0: (B,L,bh,bw,3) u8 out, the box alone; all faces of the call then share one (bw, bh)
+ * `boxes` IS A HOST POINTER -- the one place this ABI takes a host array.  The entry reads it during the call, validates every box
+ * on the host and hands the boxes to the kernels BY VALUE in their argument blocks, 32 faces per launch (a larger B is a short
+ * loop of launches): the array may be freed or changed as soon as the call returns, nothing is uploaded, no device scratch is
+ * needed, and the values are baked into the launches, so the call may be captured into a graph.
+ * Box rules, each GCFR_ERR_INVALID_ARGUMENT before any launch: 0 <= x0, x0 + bw <= Wp, 0 <= y0, y0 + bh <= Hp; bw >= w and
+ * bh >= h (the box is never smaller than the network's input); 2 bh h and 2 bw w fit 31 bits; Hp Wp < 2^31 and
+ * B ceil(Hp Wp / 1024) < 2^31.  The two axes are independent: bh / h need not equal bw / w, and neither needs to be an integer.
+ * Every operation is one separately rounded IEEE f32 operation unless marked otherwise.
+ *   Box ingest, an exact area mean in integers.  On the row axis photograph row y of the box and low-resolution row i overlap by
+ *            the integer wy(i,y) = max(0, min((y+1) h, (i+1) bh) - max(y h, i bh)), which lies in [0, h]; columns use the same
+ *            formula.  S[i,j,c] = sum of wy wx byte, an exact integer of at most 255 bh bw (64-bit).
+ *            x_lo = (float)((double)S / (255.0 bh bw)): the denominator is exact in f64, the quotient is rounded once to f32.
+ *   Up over the box, per axis and box-relative index y: N = max((2y+1) h - bh, 0), y0 = N div (2 bh), rem = N - y0 2 bh,
+ *            t = (float)((double)rem / (double)(2 bh)), y1 = min(y0 + 1, h - 1): exact integer work but for the one rounding of
+ *            t.  The lerps and their order are Up's above: horizontal a0 + tx (a1 - a0) on both rows, then top + ty (bot - top).
+ *            Both taps are always read.
+ *   Composite: inside the box the p, xl, d, m, r, v above, then byte = m > 0 ? saturate(rint((double)v)) : photo_u8 (the same
+ *            device functions as gcfr_fullres_composites_u8).  A pixel of the output window outside the box is the photograph's
+ *            byte, for every light.
+ * Refusals: everything gcfr_fullres_composites_u8 refuses (but there is no `s`), the box rules, a NULL `boxes`, `paste` outside
+ * {0, 1}, boxes of different sizes with paste = 0, and an out_u8 whose bytes overlap photo_u8's.  Allocates nothing, never
+ * synchronises.  Bit-equal to the numpy restatement (tests/fullres_box_emulation.py).  The composite moves each light's 12 bytes
+ * per four pixels as three dwords when the output window's width (Wp, or bw with paste = 0) is a multiple of 4 and out_u8 is
+ * 4-byte aligned; one element at a time otherwise (same results).  The photograph, x_lo, the mask, the taps and both weights are
+ * formed once per pixel, not once per light.
+ */
+int gcfr_ingest_box_u8(const uint8_t *photo_u8, int32_t B, int32_t Hp, int32_t Wp, const int32_t *boxes, int32_t h, int32_t w,
+                       float *x_lo_out, void *stream);
+int gcfr_fullres_composites_box_u8(const uint8_t *photo_u8, const float *x_lo, const float *rendered, const uint8_t *mask_u8,
+                                   int32_t mask_batch, int32_t B, int32_t L, int32_t Hp, int32_t Wp, const int32_t *boxes, int32_t h,
+                                   int32_t w, int32_t paste, float floor, float detail_clamp, uint8_t *out_u8, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Environment-map lighting: a lat-long radiance map integrated into the `rgb` (colour x weight per light) of the light-rig stage
  * above (csrc/gcfr_environment.hip).  Every texel belongs to the light direction nearest to it; a light's rgb is the
