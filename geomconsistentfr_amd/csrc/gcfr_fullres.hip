@@ -24,16 +24,17 @@
 // Work split of the composite: a workgroup of 256 lanes owns kQuadChunk = 1024 consecutive hi-res pixels of ONE face, four per lane
 // (gcfr_reduce.hpp).  A lane loads the photograph's bytes, forms d[3][4] and m[4] ONCE, then walks the L lights: per light only the
 // low-resolution taps of `rendered` are fetched -- each is shared by s s hi-res pixels and comes from cache -- and 12 bytes are
-// stored; the `m > 0` select is a byte mask formed once per lane and applied to the three dwords of every light.  A light's
-// 6 kWin<S> taps are requested together, in front of its arithmetic.  The photograph, x_lo and the mask are read once per pixel,
-// not once per light.
+// stored; the `m > 0` select is a byte mask formed once per lane and applied to the three dwords of every light
+// (gcfr_fullres.hpp: quad_select_mask / quad_store_selected).  A light's 6 kWin<S> taps are requested together, in front of its
+// arithmetic.  The photograph, x_lo and the mask are read once per pixel, not once per light.
 // VEC (W a multiple of four, photograph and output 4-byte aligned): lane t owns pixels 4 t .. 4 t + 3 of the chunk, all in one row;
 // the photograph's 12 bytes arrive as three dwords and every light's 12 bytes leave as three.  The four pixels share their two rows
 // and a WINDOW of kWin<S> consecutive low-resolution columns that starts at cb = floor((x + 0.5) / s - 0.5) of the first pixel
 // (-1 at the left border; columns are clamped to [0, w - 1] when loaded): pixel k's left tap is window column kP0<S>(k), a
 // compile-time constant, and its right tap the next one.  Only a pixel whose fy was clamped to 0 at the left border (2 x + 1 < s)
 // differs: its taps are columns 0 and min(1, w - 1), the latter one window column further right.  2 x kWin loads per plane instead
-// of 16.  Otherwise lane t owns pixels t, t + 256, t + 512, t + 768 and everything moves one element at a time: the same bytes.
+// of 16.  Otherwise lane t owns pixels t, t + 256, t + 512, t + 768 and everything moves one element at a time: the same bytes
+// (gcfr_fullres.hpp: composite_pixel over a Bilinear4 filled from up_tap<S>).
 // Bytes per hi-res pixel: 3 read, 3 L written; the low-resolution planes (x_lo 12, mask 1, rendered 12 L per low-res pixel) once
 // from memory.
 #include "gcfr_device.hpp"
@@ -58,13 +59,6 @@ __device__ inline void up_tap(uint32_t i, uint32_t n, uint32_t &i0, uint32_t &i1
     i1 = i0 + 1u < n ? i0 + 1u : n - 1u;
 }
 
-__device__ inline float bilerp(float a00, float a01, float a10, float a11, float tx, float ty)
-{
-    const float top = a00 + tx * (a01 - a00);
-    const float bot = a10 + tx * (a11 - a10);
-    return top + ty * (bot - top);
-}
-
 template <int S, bool VEC>
 __global__ __launch_bounds__(kQuadLanes) void fullres_composites_kernel(
     const uint8_t *__restrict__ photo, const float *__restrict__ x_lo, const float *__restrict__ rendered,
@@ -74,11 +68,7 @@ __global__ __launch_bounds__(kQuadLanes) void fullres_composites_kernel(
     const uint32_t b = blockIdx.x / chunks, ch = blockIdx.x - b * chunks;          // (uniform)
     const uint32_t q = quad_first<VEC>(ch * (uint32_t)kQuadChunk);
     const uint32_t hw = h * w;
-    const uint8_t *ph_b = photo + (size_t)b * 3u * HW;
-    const float *xl_b = x_lo + (size_t)b * 3u * hw;                                // (h,w,3)
-    const uint8_t *mk_b = mask + (size_t)b * mask_stride;
-    const float *re_b = rendered + (size_t)b * L * 3u * hw;                        // (L,3,h,w)
-    uint8_t *out_b = out + (size_t)b * L * 3u * HW;                                // (L,H,W,3)
+    const FacePlanes f = face_planes(photo, x_lo, rendered, mask, out, b, mask_stride, L, hw, HW, HW);
     if (VEC) {
         if (q >= HW)                                                               // all four pixels in range or none
             return;
@@ -115,19 +105,13 @@ __global__ __launch_bounds__(kQuadLanes) void fullres_composites_kernel(
             }
         };
         // the photograph's 12 bytes
-        const uint32_t *pw = reinterpret_cast<const uint32_t *>(ph_b + 3u * (size_t)q);
+        const uint32_t *pw = reinterpret_cast<const uint32_t *>(f.photo + 3u * (size_t)q);
         const uint32_t w3[3] = {pw[0], pw[1], pw[2]};
         float p[4][3];
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const int i = 3 * k + c;
-                p[k][c] = (float)(uint8_t)(w3[i / 4] >> (8 * (i % 4)));
-            }
+        quad_unpack_u8x3(w3, p);
         // the windows of one light's three planes
         auto load_light = [&](uint32_t l, float (&dst)[3][2][NW]) {
-            const float *re_l = re_b + (size_t)l * 3u * hw;
+            const float *re_l = f.rendered + (size_t)l * 3u * hw;
 #pragma unroll
             for (int c = 0; c < 3; ++c)
 #pragma unroll
@@ -138,14 +122,13 @@ __global__ __launch_bounds__(kQuadLanes) void fullres_composites_kernel(
         };
         float cur[3][2][NW];
         float win[2][NW], d[3][4], m[4], v[4];
-        uint32_t inside[3] = {0u, 0u, 0u};                                         // the bytes of the three dwords whose pixel has m > 0
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
 #pragma unroll
             for (int r = 0; r < 2; ++r)
 #pragma unroll
                 for (int i = 0; i < NW; ++i)
-                    win[r][i] = xl_b[3u * (size_t)(roff[r] + col[i]) + c];
+                    win[r][i] = f.x_lo[3u * (size_t)(roff[r] + col[i]) + c];
             up4(win, v);
 #pragma unroll
             for (int k = 0; k < 4; ++k)
@@ -155,31 +138,20 @@ __global__ __launch_bounds__(kQuadLanes) void fullres_composites_kernel(
         for (int r = 0; r < 2; ++r)
 #pragma unroll
             for (int i = 0; i < NW; ++i)
-                win[r][i] = mask_quotient_f32(mk_b[roff[r] + col[i]]);
+                win[r][i] = mask_quotient_f32(f.mask[roff[r] + col[i]]);
         up4(win, m);
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const int i = 3 * k + c;
-                inside[i / 4] |= m[k] > 0.0f ? 0xffu << (8 * (i % 4)) : 0u;
-            }
+        const bool relit[4] = {m[0] > 0.0f, m[1] > 0.0f, m[2] > 0.0f, m[3] > 0.0f};
+        uint32_t inside[3];                                                        // m > 0 ? the relit byte : the photograph's
+        quad_select_mask(relit, inside);
         for (uint32_t l = 0; l < L; ++l) {
             load_light(l, cur);
-            uint32_t o[3] = {0u, 0u, 0u};
+            float r[3][4];
 #pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                up4(cur[c], v);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int i = 3 * k + c;
-                    o[i / 4] |= (uint32_t)quantise_u8((double)fullres_value(p[k][c], m[k], d[c][k], v[k])) << (8 * (i % 4));
-                }
-            }
-            uint32_t *ow = reinterpret_cast<uint32_t *>(out_b + 3u * ((size_t)l * HW + q));
-#pragma unroll
-            for (int j = 0; j < 3; ++j)                                            // m > 0 ? the relit byte : the photograph's
-                ow[j] = (o[j] & inside[j]) | (w3[j] & ~inside[j]);
+            for (int c = 0; c < 3; ++c)
+                up4(cur[c], r[c]);
+            quad_store_selected(f.out + 3u * ((size_t)l * HW + q), w3, inside, [&](int k, int c) {
+                return quantise_u8((double)fullres_value(p[k][c], m[k], d[c][k], r[c][k]));
+            });
         }
     } else {
 #pragma unroll 1
@@ -192,28 +164,9 @@ __global__ __launch_bounds__(kQuadLanes) void fullres_composites_kernel(
             float ty, tx;
             up_tap<S>(y, h, y0, y1, ty);
             up_tap<S>(x, w, x0, x1, tx);
-            const uint32_t t00 = y0 * w + x0, t01 = y0 * w + x1, t10 = y1 * w + x0, t11 = y1 * w + x1;
-            uint8_t pb[3];
-            float p[3], d[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                pb[c] = ph_b[3u * (size_t)px + c];
-                p[c] = (float)pb[c];
-                const float up = bilerp(xl_b[3u * (size_t)t00 + c], xl_b[3u * (size_t)t01 + c], xl_b[3u * (size_t)t10 + c],
-                                        xl_b[3u * (size_t)t11 + c], tx, ty);
-                d[c] = detail_of(p[c], up, floor, lo, hi);
-            }
-            const float m = bilerp(mask_quotient_f32(mk_b[t00]), mask_quotient_f32(mk_b[t01]), mask_quotient_f32(mk_b[t10]),
-                                   mask_quotient_f32(mk_b[t11]), tx, ty);
-            for (uint32_t l = 0; l < L; ++l) {
-                const float *re_l = re_b + (size_t)l * 3u * hw;
-                uint8_t *o = out_b + 3u * ((size_t)l * HW + px);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const float *plane = re_l + (size_t)c * hw;
-                    o[c] = fullres_byte(pb[c], p[c], m, d[c], bilerp(plane[t00], plane[t01], plane[t10], plane[t11], tx, ty));
-                }
-            }
+            const uint8_t *pp = f.photo + 3u * (size_t)px;
+            const uint8_t pb[3] = {pp[0], pp[1], pp[2]};
+            composite_pixel(Bilinear4(y0, y1, x0, x1, w, tx, ty), pb, f, L, hw, HW, px, floor, lo, hi);
         }
     }
 }
@@ -278,31 +231,6 @@ __global__ __launch_bounds__(kQuadLanes) void ingest_photographs_kernel(const ui
     }
 }
 
-template <int S>
-void launch_composites(bool vec, dim3 grid, hipStream_t st, const uint8_t *photo, const float *x_lo, const float *rendered,
-                       const uint8_t *mask, uint32_t mask_stride, uint32_t L, uint32_t h, uint32_t w, uint32_t HW, uint32_t chunks,
-                       float floor, float lo, float hi, uint8_t *out)
-{
-    const dim3 block(kQuadLanes);
-    const uint32_t W = w * (uint32_t)S;
-    if (vec)
-        hipLaunchKernelGGL((fullres_composites_kernel<S, true>), grid, block, 0, st, photo, x_lo, rendered, mask, mask_stride, L, h, w,
-                           W, HW, chunks, floor, lo, hi, out);
-    else
-        hipLaunchKernelGGL((fullres_composites_kernel<S, false>), grid, block, 0, st, photo, x_lo, rendered, mask, mask_stride, L, h, w,
-                           W, HW, chunks, floor, lo, hi, out);
-}
-
-template <int S>
-void launch_ingest(bool vec, dim3 grid, hipStream_t st, const uint8_t *photo, uint32_t w, uint32_t hw, uint32_t chunks, float *x_lo)
-{
-    const dim3 block(kQuadLanes);
-    if (vec)
-        hipLaunchKernelGGL((ingest_photographs_kernel<S, true>), grid, block, 0, st, photo, w, hw, chunks, x_lo);
-    else
-        hipLaunchKernelGGL((ingest_photographs_kernel<S, false>), grid, block, 0, st, photo, w, hw, chunks, x_lo);
-}
-
 }  // namespace gcfr
 
 using namespace gcfr;
@@ -314,15 +242,15 @@ extern "C" int gcfr_ingest_photographs_u8(const uint8_t *photo_u8, int32_t B, in
     if (!photo_u8 || !x_lo_out || (const void *)photo_u8 == (const void *)x_lo_out || !fullres_shape(B, h, w, s, HW, hw))
         return GCFR_ERR_INVALID_ARGUMENT;
     const uint32_t chunks = (hw + kQuadChunk - 1) / kQuadChunk;
-    const bool vec = (uint32_t)w % 4u == 0 && fullres_aligned4(photo_u8) && aligned16(x_lo_out);
+    const bool vec = (uint32_t)w % 4u == 0 && aligned4(photo_u8) && aligned16(x_lo_out);
     const dim3 grid((uint32_t)B * chunks);
     hipStream_t st = (hipStream_t)stream;
-    switch (s) {
-    case 1: launch_ingest<1>(vec, grid, st, photo_u8, (uint32_t)w, hw, chunks, x_lo_out); break;
-    case 2: launch_ingest<2>(vec, grid, st, photo_u8, (uint32_t)w, hw, chunks, x_lo_out); break;
-    case 4: launch_ingest<4>(vec, grid, st, photo_u8, (uint32_t)w, hw, chunks, x_lo_out); break;
-    default: launch_ingest<8>(vec, grid, st, photo_u8, (uint32_t)w, hw, chunks, x_lo_out); break;
-    }
+    with_scale(s, [&](auto S) {
+        with_flag(vec, [&](auto V) {
+            hipLaunchKernelGGL((ingest_photographs_kernel<decltype(S)::value, decltype(V)::value>), grid, dim3(kQuadLanes), 0, st,
+                               photo_u8, (uint32_t)w, hw, chunks, x_lo_out);
+        });
+    });
     return hipGetLastError() == hipSuccess ? GCFR_OK : GCFR_ERR_LAUNCH;
 }
 
@@ -330,21 +258,22 @@ extern "C" int gcfr_fullres_composites_u8(const uint8_t *photo_u8, const float *
                                           int32_t mask_batch, int32_t B, int32_t L, int32_t h, int32_t w, int32_t s, float floor,
                                           float detail_clamp, uint8_t *out_u8, void *stream)
 {
-    uint32_t HW, hw;
-    if (!photo_u8 || !x_lo || !rendered || !mask_u8 || !out_u8 || out_u8 == photo_u8 || L < 1 || L > kFullresMaxLights ||
-        !fullres_shape(B, h, w, s, HW, hw) || (mask_batch != 1 && mask_batch != B) || !(detail_clamp >= 1.0f) || !(floor > 0.0f))
+    uint32_t HW, hw, mask_stride;
+    float lo;
+    if (!fullres_shape(B, h, w, s, HW, hw) ||
+        !fullres_operands(photo_u8, x_lo, rendered, mask_u8, out_u8, L, mask_batch, B, hw, detail_clamp, floor, mask_stride, lo) ||
+        out_u8 == photo_u8)
         return GCFR_ERR_INVALID_ARGUMENT;
-    const uint32_t chunks = (HW + kQuadChunk - 1) / kQuadChunk;
-    const uint32_t mask_stride = mask_batch == 1 ? 0u : hw;
-    const bool vec = ((uint32_t)w * (uint32_t)s) % 4u == 0 && fullres_aligned4(photo_u8) && fullres_aligned4(out_u8);
-    const float lo = 1.0f / detail_clamp;
+    const uint32_t chunks = (HW + kQuadChunk - 1) / kQuadChunk, W = (uint32_t)w * (uint32_t)s;
+    const bool vec = W % 4u == 0 && aligned4(photo_u8) && aligned4(out_u8);
     const dim3 grid((uint32_t)B * chunks);
     hipStream_t st = (hipStream_t)stream;
-    switch (s) {
-    case 1: launch_composites<1>(vec, grid, st, photo_u8, x_lo, rendered, mask_u8, mask_stride, (uint32_t)L, (uint32_t)h, (uint32_t)w, HW, chunks, floor, lo, detail_clamp, out_u8); break;
-    case 2: launch_composites<2>(vec, grid, st, photo_u8, x_lo, rendered, mask_u8, mask_stride, (uint32_t)L, (uint32_t)h, (uint32_t)w, HW, chunks, floor, lo, detail_clamp, out_u8); break;
-    case 4: launch_composites<4>(vec, grid, st, photo_u8, x_lo, rendered, mask_u8, mask_stride, (uint32_t)L, (uint32_t)h, (uint32_t)w, HW, chunks, floor, lo, detail_clamp, out_u8); break;
-    default: launch_composites<8>(vec, grid, st, photo_u8, x_lo, rendered, mask_u8, mask_stride, (uint32_t)L, (uint32_t)h, (uint32_t)w, HW, chunks, floor, lo, detail_clamp, out_u8); break;
-    }
+    with_scale(s, [&](auto S) {
+        with_flag(vec, [&](auto V) {
+            hipLaunchKernelGGL((fullres_composites_kernel<decltype(S)::value, decltype(V)::value>), grid, dim3(kQuadLanes), 0, st,
+                               photo_u8, x_lo, rendered, mask_u8, mask_stride, (uint32_t)L, (uint32_t)h, (uint32_t)w, W, HW, chunks,
+                               floor, lo, detail_clamp, out_u8);
+        });
+    });
     return hipGetLastError() == hipSuccess ? GCFR_OK : GCFR_ERR_LAUNCH;
 }

@@ -1,7 +1,17 @@
-// What the two full-resolution composites (gcfr_fullres.hip: bilinear Up; gcfr_fullres_guided.hip: joint-bilateral Up_J) share so
-// that they cannot drift: the quotient, the blend and the byte of the statement (include/gcfr.h), the vector path's column
-// offsets, and the host-side shape checks.
+// What the three full-resolution composites share so that they cannot drift (gcfr_fullres.hip: bilinear Up; gcfr_fullres_guided.hip:
+// joint-bilateral Up_J; gcfr_fullres_box.hip: bilinear Up over a face box).  include/gcfr.h is the statement; here is its ONE text:
+//   arithmetic   bilerp, detail_of (the quotient), fullres_value (the blend), fullres_byte (the byte)
+//   vector path  the 12-byte lane's select mask and its select-and-store (the pack / unpack pair is gcfr_reduce.hpp's), and the
+//                column offsets kP0 of a lane's four pixels
+//   scalar path  composite_pixel: the whole pixel, over an upsampler object whose one operation is up(value_at); Bilinear4 is the
+//                upsampler of both bilinear kernels, filled from up_tap<S> or from box_tap
+//   per face     FacePlanes / face_planes: the five base pointers of a workgroup's face
+//   host         the shape check, the operand check of the three composite entries, and with_scale / with_flag, which turn the
+//                run-time (s, vec) into template arguments
+// The three vector-path upsamplers and the two tap functions (up_tap<S>: shifts; box_tap: divisions) stay with their kernels.
 #pragma once
+
+#include <type_traits>
 
 #include "gcfr_composite.hpp"
 #include "gcfr_reduce.hpp"
@@ -16,6 +26,14 @@ constexpr int log2_of() { return S == 1 ? 0 : S == 2 ? 1 : S == 4 ? 2 : 3; }
 // less pixel 0's
 template <int S>
 constexpr int kP0(int k) { return S == 1 ? k : S == 2 ? (k + 1) / 2 : S == 4 ? k / 2 : 0; }
+
+// Up from its four taps: horizontal first on both rows, then vertical
+__device__ inline float bilerp(float a00, float a01, float a10, float a11, float tx, float ty)
+{
+    const float top = a00 + tx * (a01 - a00);
+    const float bot = a10 + tx * (a11 - a10);
+    return top + ty * (bot - top);
+}
 
 __device__ inline float detail_of(float p, float xl_up, float floor, float lo, float hi)
 {
@@ -35,7 +53,85 @@ __device__ inline uint8_t fullres_byte(uint8_t photo, float p, float m, float d,
     return m > 0.0f ? quantise_u8((double)fullres_value(p, m, d, r_up)) : photo;
 }
 
-inline bool fullres_aligned4(const void *p) { return ((uintptr_t)p & 3u) == 0; }
+// The vector path's 12 bytes (gcfr_reduce.hpp: quad_unpack_u8x3 / quad_pack_u8x3).  sel: the bytes of the three dwords whose pixel
+// is relit, formed once per lane; then per light `byte_of(k, c)` where sel is set and the photograph's own byte w3 elsewhere.
+__device__ inline void quad_select_mask(const bool (&relit)[4], uint32_t (&sel)[3])
+{
+    sel[0] = sel[1] = sel[2] = 0u;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const int i = 3 * k + c;
+            sel[i / 4] |= relit[k] ? 0xffu << (8 * (i % 4)) : 0u;
+        }
+}
+
+template <class F>
+__device__ inline void quad_store_selected(uint8_t *dst, const uint32_t (&w3)[3], const uint32_t (&sel)[3], F byte_of)
+{
+    uint32_t o[3];
+    quad_pack_u8x3(o, byte_of);
+    uint32_t *ow = reinterpret_cast<uint32_t *>(dst);
+#pragma unroll
+    for (int j = 0; j < 3; ++j)
+        ow[j] = (o[j] & sel[j]) | (w3[j] & ~sel[j]);
+}
+
+// the base pointers of face b: PN the photograph's pixels per face, WN the output window's (the same but for a box)
+struct FacePlanes {
+    const uint8_t *photo;                          // (PN,3)
+    const float *x_lo;                             // (h,w,3)
+    const uint8_t *mask;                           // (h,w)
+    const float *rendered;                         // (L,3,h,w)
+    uint8_t *out;                                  // (L,WN,3)
+};
+
+__device__ inline FacePlanes face_planes(const uint8_t *photo, const float *x_lo, const float *rendered, const uint8_t *mask,
+                                         uint8_t *out, uint32_t b, uint32_t mask_stride, uint32_t L, uint32_t hw, uint32_t PN,
+                                         uint32_t WN)
+{
+    return {photo + (size_t)b * 3u * PN, x_lo + (size_t)b * 3u * hw, mask + (size_t)b * mask_stride,
+            rendered + (size_t)b * L * 3u * hw, out + (size_t)b * L * 3u * WN};
+}
+
+// the bilinear upsampler of one pixel: Up of the plane whose value at low-resolution pixel t is value_at(t)
+struct Bilinear4 {
+    uint32_t t00, t01, t10, t11;
+    float tx, ty;
+    __device__ Bilinear4(uint32_t y0, uint32_t y1, uint32_t x0, uint32_t x1, uint32_t w, float tx_, float ty_)
+        : t00(y0 * w + x0), t01(y0 * w + x1), t10(y1 * w + x0), t11(y1 * w + x1), tx(tx_), ty(ty_) {}
+    template <class V>
+    __device__ float operator()(V value_at) const
+    {
+        return bilerp(value_at(t00), value_at(t01), value_at(t10), value_at(t11), tx, ty);
+    }
+};
+
+// The scalar path: pixel px of face f's window of WN pixels, whose photograph bytes are pb, for all L lights, one element at a
+// time: d and m once, then per light the byte.
+template <class Up>
+__device__ inline void composite_pixel(const Up &up, const uint8_t (&pb)[3], const FacePlanes &f, uint32_t L, uint32_t hw,
+                                       uint32_t WN, uint32_t px, float floor, float lo, float hi)
+{
+    float p[3], d[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        p[c] = (float)pb[c];
+        d[c] = detail_of(p[c], up([&](uint32_t t) { return f.x_lo[3u * (size_t)t + c]; }), floor, lo, hi);
+    }
+    const float m = up([&](uint32_t t) { return mask_quotient_f32(f.mask[t]); });
+    for (uint32_t l = 0; l < L; ++l) {
+        const float *re_l = f.rendered + (size_t)l * 3u * hw;
+        uint8_t *o = f.out + 3u * ((size_t)l * WN + px);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float *plane = re_l + (size_t)c * hw;
+            o[c] = fullres_byte(pb[c], p[c], m, d[c], up([&](uint32_t t) { return plane[t]; }));
+        }
+    }
+}
+
 inline bool fullres_scale_ok(int32_t s) { return s == 1 || s == 2 || s == 4 || s == 8; }
 
 // (B, h, w, s) -> the hi-res and the low-res pixel counts per face; false where a per-face pixel count or a chunk count does not
@@ -50,6 +146,42 @@ inline bool fullres_shape(int32_t B, int32_t h, int32_t w, int32_t s, uint32_t &
         return false;
     HW = (uint32_t)HW64, hw = (uint32_t)hw64;
     return true;
+}
+
+// the operands every composite entry takes, for B faces of hw low-resolution pixels -> the mask's stride per face and the lower
+// clamp of d; false where one is refused
+inline bool fullres_operands(const void *photo, const void *x_lo, const void *rendered, const void *mask, const void *out, int32_t L,
+                             int32_t mask_batch, int32_t B, uint32_t hw, float detail_clamp, float floor, uint32_t &mask_stride,
+                             float &lo)
+{
+    if (!photo || !x_lo || !rendered || !mask || !out || L < 1 || L > kFullresMaxLights || (mask_batch != 1 && mask_batch != B) ||
+        !(detail_clamp >= 1.0f) || !(floor > 0.0f))
+        return false;
+    mask_stride = mask_batch == 1 ? 0u : hw;
+    lo = 1.0f / detail_clamp;
+    return true;
+}
+
+// f(std::integral_constant<int, S>{}) for the scale s (fullres_scale_ok), f(std::bool_constant<v>{}) for a flag: a kernel's
+// template arguments from run-time values, so that an entry names its kernel and its arguments once
+template <class F>
+inline void with_scale(int32_t s, F f)
+{
+    switch (s) {
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    default: f(std::integral_constant<int, 8>{}); break;
+    }
+}
+
+template <class F>
+inline void with_flag(bool v, F f)
+{
+    if (v)
+        f(std::true_type{});
+    else
+        f(std::false_type{});
 }
 
 }  // namespace gcfr

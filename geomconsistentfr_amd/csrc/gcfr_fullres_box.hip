@@ -14,10 +14,11 @@
 //               exact in f64, the quotient is rounded once.
 //   Up          per axis and box-relative index y: N = max((2y+1) h - bh, 0), y0 = N div 2 bh, rem = N - y0 2 bh,
 //               t = (float)((double)rem / (double)(2 bh)), y1 = min(y0 + 1, h - 1): integers but for the one rounding of t.  The
-//               lerps and their order are gcfr_fullres.hip's (bilerp below is its text); both taps are always read.
+//               lerps and their order are gcfr_fullres.hpp's bilerp; both taps are always read.
 //   Composite   inside the box gcfr_fullres.hip's p, xl, d, m, r, v and byte, through the SAME device functions
-//               (gcfr_fullres.hpp: detail_of / fullres_value / fullres_byte); a pixel of the output window outside the box is the
-//               photograph's byte for every light.
+//               (gcfr_fullres.hpp: bilerp / detail_of / fullres_value / fullres_byte; the scalar path is its composite_pixel over
+//               a Bilinear4 filled from box_tap); a pixel of the output window outside the box is the photograph's byte for every
+//               light.
 //
 // The boxes arrive in a HOST array, are validated on the host and travel BY VALUE in the kernel's argument block (BoxArgs: up to
 // kBoxFaces faces per launch; more faces are a short loop of launches): nothing is uploaded, no device scratch, capture-safe.
@@ -26,8 +27,8 @@
 // output WINDOW -- the photograph (paste = 1) or the box (paste = 0); the two differ in the window's origin and size only.  A lane
 // forms the photograph's bytes, the tap indices, both weights, d[3][4] and m[4] ONCE, then walks the L lights: per light only the
 // taps of `rendered` are fetched (cache-served: each is shared by about (bh / h)(bw / w) pixels) and 12 bytes are stored.  The
-// `m > 0` select and the inside-the-box select are ONE byte mask formed once per lane; the light loop has no division and no
-// branch.  A pixel outside the box computes on the box's nearest pixel (its indices are clamped: every address stays in range)
+// `m > 0` select and the inside-the-box select are ONE byte mask (gcfr_fullres.hpp: quad_select_mask) formed once per lane; the
+// light loop has no division and no branch.  A pixel outside the box computes on the box's nearest pixel (its indices are clamped: every address stays in range)
 // and its bytes are masked away; a lane whose four pixels are all outside copies its three dwords L times instead.
 // VEC (the window's width a multiple of four, out 4-byte aligned): lane t owns pixels 4 t .. 4 t + 3 of the chunk, all in one row;
 // every light's 12 bytes leave as three dwords.  The photograph's 12 bytes arrive as three dword loads that need no alignment (a
@@ -66,13 +67,6 @@ __device__ inline uint32_t box_clamp(int32_t p, int32_t b0, int32_t nb, bool &in
     return (uint32_t)(r < 0 ? 0 : r < nb ? r : nb - 1);
 }
 
-__device__ inline float box_bilerp(float a00, float a01, float a10, float a11, float tx, float ty)
-{
-    const float top = a00 + tx * (a01 - a00);
-    const float bot = a10 + tx * (a11 - a10);
-    return top + ty * (bot - top);
-}
-
 // A plane of n floats (4 n < 2^32) behind a buffer descriptor: a load is the plane's uniform descriptor plus ONE 32-bit register of
 // byte offset per lane, where a flat load holds a 64-bit address per tap (48 of them per light, each advanced per light).
 struct PlaneF32 {
@@ -105,17 +99,13 @@ __global__ __launch_bounds__(kQuadLanes) void fullres_composites_box_kernel(
     const int32_t bx0 = boxes.x0[b], by0 = boxes.y0[b], bw = boxes.bw[b], bh = boxes.bh[b];
     const int32_t ox = paste ? 0 : bx0, oy = paste ? 0 : by0;                      // the window's origin in the photograph
     const uint32_t hw = h * w;
-    const uint8_t *ph_b = photo + (size_t)b * 3u * HWp;
-    const float *xl_b = x_lo + (size_t)b * 3u * hw;                                // (h,w,3)
-    const uint8_t *mk_b = mask + (size_t)b * mask_stride;
-    const float *re_b = rendered + (size_t)b * L * 3u * hw;                        // (L,3,h,w)
-    uint8_t *out_b = out + (size_t)b * L * 3u * WN;                                // (L, window, 3)
+    const FacePlanes f = face_planes(photo, x_lo, rendered, mask, out, b, mask_stride, L, hw, HWp, WN);
     if (VEC) {
         if (q >= WN)                                                               // all four pixels in range or none
             return;
         const uint32_t wy = q / WW, wx = q - wy * WW;
         const int32_t py = oy + (int32_t)wy, px = ox + (int32_t)wx;
-        const uint8_t *pp = ph_b + 3u * ((size_t)py * Wp + (size_t)px);
+        const uint8_t *pp = f.photo + 3u * ((size_t)py * Wp + (size_t)px);
         const uint32_t w3[3] = {load_dword_any(pp), load_dword_any(pp + 4), load_dword_any(pp + 8)};
         bool in_y, in_x[4], any = false;
         const uint32_t ry = box_clamp(py, by0, bh, in_y);
@@ -128,7 +118,7 @@ __global__ __launch_bounds__(kQuadLanes) void fullres_composites_box_kernel(
         }
         if (!any) {                                                                // the photograph's bytes for every light
             for (uint32_t l = 0; l < L; ++l) {
-                uint32_t *ow = reinterpret_cast<uint32_t *>(out_b + 3u * ((size_t)l * WN + q));
+                uint32_t *ow = reinterpret_cast<uint32_t *>(f.out + 3u * ((size_t)l * WN + q));
                 ow[0] = w3[0], ow[1] = w3[1], ow[2] = w3[2];
             }
             return;
@@ -141,32 +131,24 @@ __global__ __launch_bounds__(kQuadLanes) void fullres_composites_box_kernel(
         for (int k = 0; k < 4; ++k)
             box_tap(rx[k], w, (uint32_t)bw, c0[k], c1[k], tx[k]);
         float p[4][3];
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const int i = 3 * k + c;
-                p[k][c] = (float)(uint8_t)(w3[i / 4] >> (8 * (i % 4)));
-            }
+        quad_unpack_u8x3(w3, p);
         float d[3][4], m[4];
-        uint32_t keep[3] = {0u, 0u, 0u};                                           // the bytes of the three dwords that are relit
+        bool relit[4];
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
             const uint32_t t00 = roff[0] + c0[k], t01 = roff[0] + c1[k], t10 = roff[1] + c0[k], t11 = roff[1] + c1[k];
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
-                const float up = box_bilerp(xl_b[3u * (size_t)t00 + c], xl_b[3u * (size_t)t01 + c], xl_b[3u * (size_t)t10 + c],
-                                            xl_b[3u * (size_t)t11 + c], tx[k], ty);
+                const float up = bilerp(f.x_lo[3u * (size_t)t00 + c], f.x_lo[3u * (size_t)t01 + c], f.x_lo[3u * (size_t)t10 + c],
+                                        f.x_lo[3u * (size_t)t11 + c], tx[k], ty);
                 d[c][k] = detail_of(p[k][c], up, floor, lo, hi);
             }
-            m[k] = box_bilerp(mask_quotient_f32(mk_b[t00]), mask_quotient_f32(mk_b[t01]), mask_quotient_f32(mk_b[t10]),
-                              mask_quotient_f32(mk_b[t11]), tx[k], ty);
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const int i = 3 * k + c;
-                keep[i / 4] |= (m[k] > 0.0f && in_x[k]) ? 0xffu << (8 * (i % 4)) : 0u;
-            }
+            m[k] = bilerp(mask_quotient_f32(f.mask[t00]), mask_quotient_f32(f.mask[t01]), mask_quotient_f32(f.mask[t10]),
+                          mask_quotient_f32(f.mask[t11]), tx[k], ty);
+            relit[k] = m[k] > 0.0f && in_x[k];
         }
+        uint32_t keep[3];                                                          // relit ? the relit byte : the photograph's
+        quad_select_mask(relit, keep);
         // the taps' BYTE offsets in a plane of `rendered` (4 h w < 2^32: 2 bh h, 2 bw w < 2^31 with bh >= h, bw >= w), so that a
         // light's loads are a uniform plane address plus one 32-bit register each
         uint32_t off[4][4];
@@ -176,7 +158,7 @@ __global__ __launch_bounds__(kQuadLanes) void fullres_composites_box_kernel(
             off[k][2] = 4u * (roff[1] + c0[k]), off[k][3] = 4u * (roff[1] + c1[k]);
         }
         for (uint32_t l = 0; l < L; ++l) {
-            const float *re_l = re_b + (size_t)l * 3u * hw;                        // (uniform)
+            const float *re_l = f.rendered + (size_t)l * 3u * hw;                  // (uniform)
             float tap[3][4][4];                                                    // a light's 48 taps, requested together
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
@@ -187,19 +169,10 @@ __global__ __launch_bounds__(kQuadLanes) void fullres_composites_box_kernel(
                     for (int j = 0; j < 4; ++j)
                         tap[c][k][j] = plane.at(off[k][j]);
             }
-            uint32_t o[3] = {0u, 0u, 0u};
-#pragma unroll
-            for (int c = 0; c < 3; ++c)
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int i = 3 * k + c;
-                    const float r = box_bilerp(tap[c][k][0], tap[c][k][1], tap[c][k][2], tap[c][k][3], tx[k], ty);
-                    o[i / 4] |= (uint32_t)quantise_u8((double)fullres_value(p[k][c], m[k], d[c][k], r)) << (8 * (i % 4));
-                }
-            uint32_t *ow = reinterpret_cast<uint32_t *>(out_b + 3u * ((size_t)l * WN + q));
-#pragma unroll
-            for (int j = 0; j < 3; ++j)                                            // relit ? the relit byte : the photograph's
-                ow[j] = (o[j] & keep[j]) | (w3[j] & ~keep[j]);
+            quad_store_selected(f.out + 3u * ((size_t)l * WN + q), w3, keep, [&](int k, int c) {
+                const float r = bilerp(tap[c][k][0], tap[c][k][1], tap[c][k][2], tap[c][k][3], tx[k], ty);
+                return quantise_u8((double)fullres_value(p[k][c], m[k], d[c][k], r));
+            });
         }
     } else {
 #pragma unroll 1
@@ -209,13 +182,13 @@ __global__ __launch_bounds__(kQuadLanes) void fullres_composites_box_kernel(
                 continue;
             const uint32_t wy = px_w / WW, wx = px_w - wy * WW;
             const int32_t py = oy + (int32_t)wy, px = ox + (int32_t)wx;
-            const uint8_t *pp = ph_b + 3u * ((size_t)py * Wp + (size_t)px);
+            const uint8_t *pp = f.photo + 3u * ((size_t)py * Wp + (size_t)px);
             const uint8_t pb[3] = {pp[0], pp[1], pp[2]};
             bool in_y, in_x;
             const uint32_t ry = box_clamp(py, by0, bh, in_y), rx = box_clamp(px, bx0, bw, in_x);
             if (!(in_y && in_x)) {
                 for (uint32_t l = 0; l < L; ++l) {
-                    uint8_t *o = out_b + 3u * ((size_t)l * WN + px_w);
+                    uint8_t *o = f.out + 3u * ((size_t)l * WN + px_w);
                     o[0] = pb[0], o[1] = pb[1], o[2] = pb[2];
                 }
                 continue;
@@ -224,26 +197,7 @@ __global__ __launch_bounds__(kQuadLanes) void fullres_composites_box_kernel(
             float ty, tx;
             box_tap(ry, h, (uint32_t)bh, y0, y1, ty);
             box_tap(rx, w, (uint32_t)bw, x0, x1, tx);
-            const uint32_t t00 = y0 * w + x0, t01 = y0 * w + x1, t10 = y1 * w + x0, t11 = y1 * w + x1;
-            float p[3], d[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                p[c] = (float)pb[c];
-                const float up = box_bilerp(xl_b[3u * (size_t)t00 + c], xl_b[3u * (size_t)t01 + c], xl_b[3u * (size_t)t10 + c],
-                                            xl_b[3u * (size_t)t11 + c], tx, ty);
-                d[c] = detail_of(p[c], up, floor, lo, hi);
-            }
-            const float m = box_bilerp(mask_quotient_f32(mk_b[t00]), mask_quotient_f32(mk_b[t01]), mask_quotient_f32(mk_b[t10]),
-                                       mask_quotient_f32(mk_b[t11]), tx, ty);
-            for (uint32_t l = 0; l < L; ++l) {
-                const float *re_l = re_b + (size_t)l * 3u * hw;
-                uint8_t *o = out_b + 3u * ((size_t)l * WN + px_w);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const float *plane = re_l + (size_t)c * hw;
-                    o[c] = fullres_byte(pb[c], p[c], m, d[c], box_bilerp(plane[t00], plane[t01], plane[t10], plane[t11], tx, ty));
-                }
-            }
+            composite_pixel(Bilinear4(y0, y1, x0, x1, w, tx, ty), pb, f, L, hw, WN, px_w, floor, lo, hi);
         }
     }
 }
@@ -353,10 +307,11 @@ extern "C" int gcfr_fullres_composites_box_u8(const uint8_t *photo_u8, const flo
                                               int32_t h, int32_t w, int32_t paste, float floor, float detail_clamp, uint8_t *out_u8,
                                               void *stream)
 {
-    uint32_t HWp, hw;
-    if (!photo_u8 || !x_lo || !rendered || !mask_u8 || !out_u8 || !boxes || L < 1 || L > kFullresMaxLights ||
-        (paste != 0 && paste != 1) || !box_shape(B, Hp, Wp, h, w, HWp, hw) || (mask_batch != 1 && mask_batch != B) ||
-        !(detail_clamp >= 1.0f) || !(floor > 0.0f) || !boxes_ok(boxes, B, Hp, Wp, h, w, paste == 0))
+    uint32_t HWp, hw, mask_stride;
+    float lo;
+    if (!boxes || (paste != 0 && paste != 1) || !box_shape(B, Hp, Wp, h, w, HWp, hw) ||
+        !fullres_operands(photo_u8, x_lo, rendered, mask_u8, out_u8, L, mask_batch, B, hw, detail_clamp, floor, mask_stride, lo) ||
+        !boxes_ok(boxes, B, Hp, Wp, h, w, paste == 0))
         return GCFR_ERR_INVALID_ARGUMENT;
     const uint32_t WW = paste ? (uint32_t)Wp : (uint32_t)boxes[2];
     const uint32_t WN = paste ? HWp : (uint32_t)boxes[2] * (uint32_t)boxes[3];     // (<= Hp Wp)
@@ -366,10 +321,7 @@ extern "C" int gcfr_fullres_composites_box_u8(const uint8_t *photo_u8, const flo
     if (oa < pe && pa < oe)
         return GCFR_ERR_INVALID_ARGUMENT;
     const uint32_t chunks = (WN + kQuadChunk - 1) / kQuadChunk;
-    const uint32_t mask_stride = mask_batch == 1 ? 0u : hw;
-    const bool vec = WW % 4u == 0 && fullres_aligned4(out_u8);
-    const float lo = 1.0f / detail_clamp;
-    const dim3 block(kQuadLanes);
+    const bool vec = WW % 4u == 0 && aligned4(out_u8);
     hipStream_t st = (hipStream_t)stream;
     for (int32_t b0 = 0; b0 < B; b0 += kBoxFaces) {
         const int32_t n = B - b0 < kBoxFaces ? B - b0 : kBoxFaces;
@@ -379,12 +331,11 @@ extern "C" int gcfr_fullres_composites_box_u8(const uint8_t *photo_u8, const flo
         const float *xl = x_lo + (size_t)b0 * 3u * hw, *re = rendered + (size_t)b0 * (size_t)L * 3u * hw;
         const uint8_t *mk = mask_u8 + (size_t)b0 * mask_stride;
         uint8_t *o = out_u8 + (size_t)b0 * (size_t)L * 3u * WN;
-        if (vec)
-            hipLaunchKernelGGL((fullres_composites_box_kernel<true>), grid, block, 0, st, ph, xl, re, mk, mask_stride, (uint32_t)L,
-                               (uint32_t)h, (uint32_t)w, (uint32_t)Wp, HWp, WW, WN, chunks, paste, floor, lo, detail_clamp, args, o);
-        else
-            hipLaunchKernelGGL((fullres_composites_box_kernel<false>), grid, block, 0, st, ph, xl, re, mk, mask_stride, (uint32_t)L,
-                               (uint32_t)h, (uint32_t)w, (uint32_t)Wp, HWp, WW, WN, chunks, paste, floor, lo, detail_clamp, args, o);
+        with_flag(vec, [&](auto V) {
+            hipLaunchKernelGGL((fullres_composites_box_kernel<decltype(V)::value>), grid, dim3(kQuadLanes), 0, st, ph, xl, re, mk,
+                               mask_stride, (uint32_t)L, (uint32_t)h, (uint32_t)w, (uint32_t)Wp, HWp, WW, WN, chunks, paste, floor, lo,
+                               detail_clamp, args, o);
+        });
     }
     return hipGetLastError() == hipSuccess ? GCFR_OK : GCFR_ERR_LAUNCH;
 }

@@ -18,7 +18,9 @@
 //               is rounded.  All 16 taps are always read: a tap of weight 0 still carries a NaN.
 //   Composite   gcfr_fullres.hip's with Up_J in all three places and the SAME wn: d = detail_of(p, Up_J(x_lo[..., c])),
 //               m = Up_J((float)mask_u8 / 255.0f), v = fullres_value(p, m, d, Up_J(rendered[b, l, c])),
-//               byte = m > 0 ? quantise_u8((double)v) : photo_u8   (gcfr_fullres.hpp, gcfr_composite.hpp: called, not copied)
+//               byte = m > 0 ? quantise_u8((double)v) : photo_u8   (gcfr_fullres.hpp, gcfr_composite.hpp: called, not copied;
+//               the scalar path is gcfr_fullres.hpp's composite_pixel over a Guided16, the vector path's 12 bytes go through its
+//               quad_select_mask / quad_store_selected)
 //
 // Work split: gcfr_fullres.hip's.  A workgroup of 256 lanes owns kQuadChunk = 1024 consecutive hi-res pixels of ONE face, four per
 // lane.  ONCE per pixel: the 16 normalised weights (48 guide values, 16 divisions for k and one for rcp), d[3] and m.  PER LIGHT:
@@ -69,6 +71,22 @@ __device__ inline float guided_range(const float (&p)[3], float x0, float x1, fl
     return 1.0f / (1.0f + d2 * inv);
 }
 
+// the joint-bilateral upsampler of one pixel (the scalar path): the 16 taps and their normalised weights, row-major; Up_J of the
+// plane whose value at low-resolution pixel t is value_at(t)
+struct Guided16 {
+    uint32_t tap[16];
+    float wn[16];
+    template <class V>
+    __device__ float operator()(V value_at) const
+    {
+        float acc = wn[0] * value_at(tap[0]);
+#pragma unroll
+        for (int t = 1; t < 16; ++t)
+            acc = acc + wn[t] * value_at(tap[t]);
+        return acc;
+    }
+};
+
 template <int S, bool VEC>
 __global__ __launch_bounds__(kQuadLanes) void fullres_composites_guided_kernel(
     const uint8_t *__restrict__ photo, const float *__restrict__ x_lo, const float *__restrict__ rendered,
@@ -78,11 +96,7 @@ __global__ __launch_bounds__(kQuadLanes) void fullres_composites_guided_kernel(
     const uint32_t b = blockIdx.x / chunks, ch = blockIdx.x - b * chunks;          // (uniform)
     const uint32_t q = quad_first<VEC>(ch * (uint32_t)kQuadChunk);
     const uint32_t hw = h * w;
-    const uint8_t *ph_b = photo + (size_t)b * 3u * HW;
-    const float *xl_b = x_lo + (size_t)b * 3u * hw;                                // (h,w,3)
-    const uint8_t *mk_b = mask + (size_t)b * mask_stride;
-    const float *re_b = rendered + (size_t)b * L * 3u * hw;                        // (L,3,h,w)
-    uint8_t *out_b = out + (size_t)b * L * 3u * HW;                                // (L,H,W,3)
+    const FacePlanes f = face_planes(photo, x_lo, rendered, mask, out, b, mask_stride, L, hw, HW, HW);
     if (VEC) {
         if (q >= HW)                                                               // all four pixels in range or none
             return;
@@ -114,16 +128,10 @@ __global__ __launch_bounds__(kQuadLanes) void fullres_composites_guided_kernel(
             return here;
         };
         // the photograph's 12 bytes
-        const uint32_t *pw = reinterpret_cast<const uint32_t *>(ph_b + 3u * (size_t)q);
+        const uint32_t *pw = reinterpret_cast<const uint32_t *>(f.photo + 3u * (size_t)q);
         const uint32_t w3[3] = {pw[0], pw[1], pw[2]};
         float p[4][3];
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const int i = 3 * k + c;
-                p[k][c] = (float)(uint8_t)(w3[i / 4] >> (8 * (i % 4)));
-            }
+        quad_unpack_u8x3(w3, p);
         // Up_J of one plane at the lane's four pixels
         float wn[4][16];
         auto up4 = [&](const float (&win)[4][NW], float (&v)[4]) {
@@ -146,7 +154,7 @@ __global__ __launch_bounds__(kQuadLanes) void fullres_composites_guided_kernel(
                 for (int j = 0; j < 4; ++j)
 #pragma unroll
                     for (int i = 0; i < NW; ++i)
-                        xw[c][j][i] = xl_b[3u * (size_t)(roff[j] + col[i]) + c];
+                        xw[c][j][i] = f.x_lo[3u * (size_t)(roff[j] + col[i]) + c];
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
                 float sx[4];
@@ -176,21 +184,16 @@ __global__ __launch_bounds__(kQuadLanes) void fullres_composites_guided_kernel(
             for (int j = 0; j < 4; ++j)
 #pragma unroll
                 for (int i = 0; i < NW; ++i)
-                    mw[j][i] = mask_quotient_f32(mk_b[roff[j] + col[i]]);
+                    mw[j][i] = mask_quotient_f32(f.mask[roff[j] + col[i]]);
             up4(mw, m);
         }
-        uint32_t inside[3] = {0u, 0u, 0u};                                         // the bytes of the three dwords whose pixel has m > 0
-#pragma unroll
-        for (int k = 0; k < 4; ++k)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                const int i = 3 * k + c;
-                inside[i / 4] |= m[k] > 0.0f ? 0xffu << (8 * (i % 4)) : 0u;
-            }
+        const bool relit[4] = {m[0] > 0.0f, m[1] > 0.0f, m[2] > 0.0f, m[3] > 0.0f};
+        uint32_t inside[3];                                                        // m > 0 ? the relit byte : the photograph's
+        quad_select_mask(relit, inside);
         // a light's three windows; the NEXT light's are requested before this light's arithmetic, which then covers their way
         // from the cache (one trip past the end reloads the last light: in bounds, unused)
         auto load_light = [&](uint32_t l, float (&dst)[3][4][NW]) {
-            const float *re_l = re_b + (size_t)l * 3u * hw;
+            const float *re_l = f.rendered + (size_t)l * 3u * hw;
 #pragma unroll
             for (int c = 0; c < 3; ++c)
 #pragma unroll
@@ -204,20 +207,13 @@ __global__ __launch_bounds__(kQuadLanes) void fullres_composites_guided_kernel(
         for (uint32_t l = 0; l < L; ++l) {
             load_light(l + 1u < L ? l + 1u : l, nxt);
             __builtin_amdgcn_sched_barrier(0);                                     // (the loads stay in front of the arithmetic)
-            uint32_t o[3] = {0u, 0u, 0u};
+            float r[3][4];
 #pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                up4(cur[c], v);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    const int i = 3 * k + c;
-                    o[i / 4] |= (uint32_t)quantise_u8((double)fullres_value(p[k][c], m[k], d[c][k], v[k])) << (8 * (i % 4));
-                }
-            }
-            uint32_t *ow = reinterpret_cast<uint32_t *>(out_b + 3u * ((size_t)l * HW + q));
-#pragma unroll
-            for (int j = 0; j < 3; ++j)                                            // m > 0 ? the relit byte : the photograph's
-                ow[j] = (o[j] & inside[j]) | (w3[j] & ~inside[j]);
+            for (int c = 0; c < 3; ++c)
+                up4(cur[c], r[c]);
+            quad_store_selected(f.out + 3u * ((size_t)l * HW + q), w3, inside, [&](int k, int c) {
+                return quantise_u8((double)fullres_value(p[k][c], m[k], d[c][k], r[c][k]));
+            });
             __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
             for (int c = 0; c < 3; ++c)
@@ -234,68 +230,31 @@ __global__ __launch_bounds__(kQuadLanes) void fullres_composites_guided_kernel(
             if (px >= HW)
                 continue;
             const uint32_t y = px / W, x = px - y * W;
-            uint32_t ty[4], tx[4], tap[16];
-            float sy[4], sx[4], wn[16];
+            uint32_t ty[4], tx[4];
+            float sy[4], sx[4];
             guided_tap<S>(y, h, ty, sy);
             guided_tap<S>(x, w, tx, sx);
+            Guided16 up;
 #pragma unroll
             for (int t = 0; t < 16; ++t)
-                tap[t] = ty[t / 4] * w + tx[t % 4];
-            auto up = [&](auto value_at) {
-                float acc = wn[0] * value_at(tap[0]);
-#pragma unroll
-                for (int t = 1; t < 16; ++t)
-                    acc = acc + wn[t] * value_at(tap[t]);
-                return acc;
-            };
-            uint8_t pb[3];
-            float p[3], d[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                pb[c] = ph_b[3u * (size_t)px + c];
-                p[c] = (float)pb[c];
-            }
+                up.tap[t] = ty[t / 4] * w + tx[t % 4];
+            const uint8_t *pp = f.photo + 3u * (size_t)px;
+            const uint8_t pb[3] = {pp[0], pp[1], pp[2]};
+            const float p[3] = {(float)pb[0], (float)pb[1], (float)pb[2]};
             float den = 0.0f;
 #pragma unroll
             for (int t = 0; t < 16; ++t) {
-                const float *g = xl_b + 3u * (size_t)tap[t];
-                wn[t] = (sy[t / 4] * sx[t % 4]) * guided_range(p, g[0], g[1], g[2], inv);
-                den = t == 0 ? wn[0] : den + wn[t];
+                const float *g = f.x_lo + 3u * (size_t)up.tap[t];
+                up.wn[t] = (sy[t / 4] * sx[t % 4]) * guided_range(p, g[0], g[1], g[2], inv);
+                den = t == 0 ? up.wn[0] : den + up.wn[t];
             }
             const float rcp = 1.0f / den;
 #pragma unroll
             for (int t = 0; t < 16; ++t)
-                wn[t] = wn[t] * rcp;
-#pragma unroll
-            for (int c = 0; c < 3; ++c)
-                d[c] = detail_of(p[c], up([&](uint32_t t) { return xl_b[3u * (size_t)t + c]; }), floor, lo, hi);
-            const float m = up([&](uint32_t t) { return mask_quotient_f32(mk_b[t]); });
-            for (uint32_t l = 0; l < L; ++l) {
-                const float *re_l = re_b + (size_t)l * 3u * hw;
-                uint8_t *o = out_b + 3u * ((size_t)l * HW + px);
-#pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    const float *plane = re_l + (size_t)c * hw;
-                    o[c] = fullres_byte(pb[c], p[c], m, d[c], up([&](uint32_t t) { return plane[t]; }));
-                }
-            }
+                up.wn[t] = up.wn[t] * rcp;
+            composite_pixel(up, pb, f, L, hw, HW, px, floor, lo, hi);
         }
     }
-}
-
-template <int S>
-void launch_composites_guided(bool vec, dim3 grid, hipStream_t st, const uint8_t *photo, const float *x_lo, const float *rendered,
-                              const uint8_t *mask, uint32_t mask_stride, uint32_t L, uint32_t h, uint32_t w, uint32_t HW,
-                              uint32_t chunks, float floor, float lo, float hi, float inv, uint8_t *out)
-{
-    const dim3 block(kQuadLanes);
-    const uint32_t W = w * (uint32_t)S;
-    if (vec)
-        hipLaunchKernelGGL((fullres_composites_guided_kernel<S, true>), grid, block, 0, st, photo, x_lo, rendered, mask, mask_stride, L,
-                           h, w, W, HW, chunks, floor, lo, hi, inv, out);
-    else
-        hipLaunchKernelGGL((fullres_composites_guided_kernel<S, false>), grid, block, 0, st, photo, x_lo, rendered, mask, mask_stride, L,
-                           h, w, W, HW, chunks, floor, lo, hi, inv, out);
 }
 
 }  // namespace gcfr
@@ -307,23 +266,23 @@ extern "C" int gcfr_fullres_composites_guided_u8(const uint8_t *photo_u8, const 
                                                  int32_t s, float floor, float detail_clamp, float range_sigma, uint8_t *out_u8,
                                                  void *stream)
 {
-    uint32_t HW, hw;
-    if (!photo_u8 || !x_lo || !rendered || !mask_u8 || !out_u8 || out_u8 == photo_u8 || L < 1 || L > kFullresMaxLights ||
-        !fullres_shape(B, h, w, s, HW, hw) || (mask_batch != 1 && mask_batch != B) || !(detail_clamp >= 1.0f) || !(floor > 0.0f) ||
-        !(range_sigma > 0.0f))
+    uint32_t HW, hw, mask_stride;
+    float lo;
+    if (!fullres_shape(B, h, w, s, HW, hw) ||
+        !fullres_operands(photo_u8, x_lo, rendered, mask_u8, out_u8, L, mask_batch, B, hw, detail_clamp, floor, mask_stride, lo) ||
+        out_u8 == photo_u8 || !(range_sigma > 0.0f))
         return GCFR_ERR_INVALID_ARGUMENT;
-    const uint32_t chunks = (HW + kQuadChunk - 1) / kQuadChunk;
-    const uint32_t mask_stride = mask_batch == 1 ? 0u : hw;
-    const bool vec = ((uint32_t)w * (uint32_t)s) % 4u == 0 && fullres_aligned4(photo_u8) && fullres_aligned4(out_u8);
-    const float lo = 1.0f / detail_clamp;
+    const uint32_t chunks = (HW + kQuadChunk - 1) / kQuadChunk, W = (uint32_t)w * (uint32_t)s;
+    const bool vec = W % 4u == 0 && aligned4(photo_u8) && aligned4(out_u8);
     const float inv = 1.0f / (range_sigma * range_sigma);                          // +inf -> 0: the spatial tent alone
     const dim3 grid((uint32_t)B * chunks);
     hipStream_t st = (hipStream_t)stream;
-    switch (s) {
-    case 1: launch_composites_guided<1>(vec, grid, st, photo_u8, x_lo, rendered, mask_u8, mask_stride, (uint32_t)L, (uint32_t)h, (uint32_t)w, HW, chunks, floor, lo, detail_clamp, inv, out_u8); break;
-    case 2: launch_composites_guided<2>(vec, grid, st, photo_u8, x_lo, rendered, mask_u8, mask_stride, (uint32_t)L, (uint32_t)h, (uint32_t)w, HW, chunks, floor, lo, detail_clamp, inv, out_u8); break;
-    case 4: launch_composites_guided<4>(vec, grid, st, photo_u8, x_lo, rendered, mask_u8, mask_stride, (uint32_t)L, (uint32_t)h, (uint32_t)w, HW, chunks, floor, lo, detail_clamp, inv, out_u8); break;
-    default: launch_composites_guided<8>(vec, grid, st, photo_u8, x_lo, rendered, mask_u8, mask_stride, (uint32_t)L, (uint32_t)h, (uint32_t)w, HW, chunks, floor, lo, detail_clamp, inv, out_u8); break;
-    }
+    with_scale(s, [&](auto S) {
+        with_flag(vec, [&](auto V) {
+            hipLaunchKernelGGL((fullres_composites_guided_kernel<decltype(S)::value, decltype(V)::value>), grid, dim3(kQuadLanes), 0,
+                               st, photo_u8, x_lo, rendered, mask_u8, mask_stride, (uint32_t)L, (uint32_t)h, (uint32_t)w, W, HW,
+                               chunks, floor, lo, detail_clamp, inv, out_u8);
+        });
+    });
     return hipGetLastError() == hipSuccess ? GCFR_OK : GCFR_ERR_LAUNCH;
 }

@@ -1,5 +1,6 @@
-// Device primitives shared by the fused heads (gcfr_losses.hip, gcfr_supervised_losses.hip, gcfr_light_rig.hip, gcfr_rig_frames.hip) and the metrics
-// of gcfr_dataset.hip: the fixed-order f64 sums and the four-pixels-per-lane access.  (gcfr_backward.hip keeps its own DPP
+// Device primitives shared by the fused heads (gcfr_losses.hip, gcfr_supervised_losses.hip, gcfr_light_rig.hip, gcfr_rig_frames.hip), the
+// full-resolution composites (gcfr_fullres.hpp) and the metrics of gcfr_dataset.hip: the fixed-order f64 sums, the four-pixels-per-lane
+// access and, for the composites, a lane's 12 bytes of four uint8 RGB pixels.  (gcfr_backward.hip keeps its own DPP
 // reductions, whose totals live in lane 0 only.)
 #pragma once
 
@@ -85,6 +86,35 @@ __device__ inline void quad_store(float *__restrict__ plane, uint32_t q, uint32_
     }
 }
 
+// A lane's four pixels of three interleaved uint8 channels are 12 consecutive bytes, three dwords: byte 3 k + c is channel c of
+// pixel k.  The pair below turns the dwords into p[k][c] and packs `byte_of(k, c)` (-> uint8_t) into them, a channel at a time (the
+// order the full-resolution composites were measured with; gcfr_rig_frames.hip packs a pixel at a time and keeps its own loop:
+// through this one its vector kernel came out seven instructions longer).
+__device__ inline void quad_unpack_u8x3(const uint32_t (&w3)[3], float (&p)[4][3])
+{
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const int i = 3 * k + c;
+            p[k][c] = (float)(uint8_t)(w3[i / 4] >> (8 * (i % 4)));
+        }
+}
+
+template <class F>
+__device__ inline void quad_pack_u8x3(uint32_t (&o)[3], F byte_of)
+{
+    o[0] = o[1] = o[2] = 0u;
+#pragma unroll
+    for (int c = 0; c < 3; ++c)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int i = 3 * k + c;
+            o[i / 4] |= (uint32_t)byte_of(k, c) << (8 * (i % 4));
+        }
+}
+
+inline bool aligned4(const void *p) { return ((uintptr_t)p & 3u) == 0; }
 inline bool aligned16(const void *p) { return ((uintptr_t)p & 15u) == 0; }
 
 // may the planes of HW pixels each behind these pointers be moved 16 bytes at a time?  (an absent plane, NULL, counts as aligned)

@@ -159,8 +159,6 @@ __global__ __launch_bounds__(kQuadLanes) void light_rig_frames_kernel(
     }
 }
 
-inline bool aligned4(const void *p) { return ((uintptr_t)p & 3u) == 0; }
-
 }  // namespace gcfr
 
 using namespace gcfr;

@@ -183,16 +183,24 @@ def _as_photographs(photos_u8, device) -> torch.Tensor:
     return _as(t, device, torch.uint8, single=3)
 
 
+def _relight_photographs(model, photos_u8, mask_u8, lights, ambient, focal, device, composite_mask_u8, epoch, ingest, composite, light_rgb=None, rig=False):
+    """Every full-resolution and in-photograph entry, on the device: `ingest(photos)` -> the network's input x, ONE `forward_lights`
+    pass on it, for a `rig` `lighting.combine_lights`' one image per face under `light_rgb`, then `composite(photos, x, rendered, cm)`"""
+    photos = _as_photographs(photos_u8, device)
+    x = ingest(photos)
+    out, cm, _transfer = _lights_pass(model, x, mask_u8, lights, ambient, focal, device, composite_mask_u8, epoch)
+    return composite(photos, x, combine_lights(out[8], out[0], _as(light_rgb, x.device, single=2).contiguous())[0] if rig else out[5], cm)
+
+
 @torch.no_grad()
 def relight_lights_fullres_device(model, photos_u8, mask_u8, lights, scale: int, ambient: float = 0.5, focal: float = None,
                                   device="cuda", composite_mask_u8=None, epoch: int = 200, detail_clamp: float = 4.0,
                                   floor: float = 1.0, upsample: str = "bilinear", range_sigma: float = 20.0) -> torch.Tensor:
     """`relight_lights_fullres` up to the bytes ON THE DEVICE: (B,L,H,W,3) uint8 tensor, nothing copied back.  `photos_u8` /
     `mask_u8` / `lights` may already be device tensors."""
-    photos = _as_photographs(photos_u8, device)
-    x = pp.ingest_photographs_device(photos, scale)
-    out, cm, _transfer = _lights_pass(model, x, mask_u8, lights, ambient, focal, device, composite_mask_u8, epoch)
-    return pp.fullres_composites_device(photos, x, out[5], cm, scale, detail_clamp, floor, upsample=upsample, range_sigma=range_sigma)
+    return _relight_photographs(model, photos_u8, mask_u8, lights, ambient, focal, device, composite_mask_u8, epoch,
+                                lambda ph: pp.ingest_photographs_device(ph, scale),
+                                lambda *a: pp.fullres_composites_device(*a, scale, detail_clamp, floor, upsample=upsample, range_sigma=range_sigma))
 
 
 @torch.no_grad()
@@ -218,11 +226,10 @@ def relight_rig_fullres_device(model, photos_u8, mask_u8, lights, light_rgb, sca
                                device="cuda", composite_mask_u8=None, epoch: int = 200, detail_clamp: float = 4.0,
                                floor: float = 1.0, upsample: str = "bilinear", range_sigma: float = 20.0) -> torch.Tensor:
     """`relight_rig_fullres` up to the bytes ON THE DEVICE: (B,H,W,3) uint8 tensor, nothing copied back."""
-    photos = _as_photographs(photos_u8, device)
-    x = pp.ingest_photographs_device(photos, scale)
-    out, cm, _transfer = _lights_pass(model, x, mask_u8, lights, ambient, focal, device, composite_mask_u8, epoch)
-    rendered, _ = combine_lights(out[8], out[0], _as(light_rgb, x.device, single=2).contiguous())
-    return pp.fullres_composites_device(photos, x, rendered, cm, scale, detail_clamp, floor, upsample=upsample, range_sigma=range_sigma)
+    return _relight_photographs(model, photos_u8, mask_u8, lights, ambient, focal, device, composite_mask_u8, epoch,
+                                lambda ph: pp.ingest_photographs_device(ph, scale),
+                                lambda *a: pp.fullres_composites_device(*a, scale, detail_clamp, floor, upsample=upsample, range_sigma=range_sigma),
+                                light_rgb, rig=True)
 
 
 @torch.no_grad()
@@ -257,10 +264,9 @@ def relight_lights_in_photograph_device(model, photos_u8, boxes, mask_u8, lights
     """`relight_lights_in_photograph` up to the bytes ON THE DEVICE: (B,L,Hp,Wp,3) uint8 tensor (`paste=False`: (B,L,bh,bw,3)),
     nothing copied back.  `photos_u8` / `mask_u8` / `lights` may already be device tensors; `boxes` stay on the host."""
     _check_host_boxes(boxes)
-    photos = _as_photographs(photos_u8, device)
-    x = pp.ingest_box_device(photos, boxes, _network_size(mask_u8))
-    out, cm, _transfer = _lights_pass(model, x, mask_u8, lights, ambient, focal, device, composite_mask_u8, epoch)
-    return pp.fullres_box_composites_device(photos, boxes, x, out[5], cm, detail_clamp, floor, paste=paste)
+    return _relight_photographs(model, photos_u8, mask_u8, lights, ambient, focal, device, composite_mask_u8, epoch,
+                                lambda ph: pp.ingest_box_device(ph, boxes, _network_size(mask_u8)),
+                                lambda ph, *a: pp.fullres_box_composites_device(ph, boxes, *a, detail_clamp, floor, paste=paste))
 
 
 @torch.no_grad()
@@ -288,11 +294,10 @@ def relight_rig_in_photograph_device(model, photos_u8, boxes, mask_u8, lights, l
     """`relight_rig_in_photograph` up to the bytes ON THE DEVICE: (B,Hp,Wp,3) uint8 tensor (`paste=False`: (B,bh,bw,3)), nothing
     copied back."""
     _check_host_boxes(boxes)
-    photos = _as_photographs(photos_u8, device)
-    x = pp.ingest_box_device(photos, boxes, _network_size(mask_u8))
-    out, cm, _transfer = _lights_pass(model, x, mask_u8, lights, ambient, focal, device, composite_mask_u8, epoch)
-    rendered, _ = combine_lights(out[8], out[0], _as(light_rgb, x.device, single=2).contiguous())
-    return pp.fullres_box_composites_device(photos, boxes, x, rendered, cm, detail_clamp, floor, paste=paste)
+    return _relight_photographs(model, photos_u8, mask_u8, lights, ambient, focal, device, composite_mask_u8, epoch,
+                                lambda ph: pp.ingest_box_device(ph, boxes, _network_size(mask_u8)),
+                                lambda ph, *a: pp.fullres_box_composites_device(ph, boxes, *a, detail_clamp, floor, paste=paste),
+                                light_rgb, rig=True)
 
 
 @torch.no_grad()

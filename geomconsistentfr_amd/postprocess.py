@@ -110,13 +110,14 @@ FULLRES_SCALES = (1, 2, 4, 8)       # photograph side / network side (csrc/gcfr_
 FULLRES_MAX_LIGHTS = 4096
 
 
-def _check_photographs(photo_u8, scale, what):
-    """-> (B, h, w, s) of uint8 photographs (B, s h, s w, 3), or GcfrError (where they live is the caller's last check)"""
+def _check_photographs(photo_u8, scale, what, boxed=False):
+    """-> (B, h, w, s) of uint8 photographs (B, s h, s w, 3) within the kernels' 31-bit limits, or GcfrError (where they live is the
+    caller's last check).  `boxed`: photographs (B,Hp,Wp,3) of any size but empty, as the box entries take them (at scale 1)."""
     import torch
     from . import _lib
     _lib.check_tensors(what, [("photographs", photo_u8)], photographs=torch.uint8)
-    if photo_u8.dim() != 4 or photo_u8.shape[-1] != 3:
-        raise _lib.GcfrError("%s: photographs must be a uint8 tensor (B,H,W,3); got %s" % (what, tuple(photo_u8.shape)))
+    if photo_u8.dim() != 4 or photo_u8.shape[-1] != 3 or (boxed and min(photo_u8.shape) < 1):
+        raise _lib.GcfrError("%s: photographs must be a uint8 tensor (B,%s,3); got %s" % (what, "Hp,Wp" if boxed else "H,W", tuple(photo_u8.shape)))
     if isinstance(scale, bool) or not isinstance(scale, int) or scale not in FULLRES_SCALES:
         raise _lib.GcfrError("%s: scale must be one of %s; got %r" % (what, FULLRES_SCALES, scale))
     B, H, W, _ = photo_u8.shape
@@ -125,6 +126,34 @@ def _check_photographs(photo_u8, scale, what):
     if H * W > 0x7fffffff or B * ((H * W + 1023) // 1024) > 0x7fffffff:
         raise _lib.GcfrError("%s: %d photographs of %d x %d pixels do not fit the kernels' 31-bit pixel and chunk counts" % (what, B, H, W))
     return B, H // scale, W // scale, scale
+
+
+def _check_composite_tensors(what, x_lo, rendered, mask_u8, out):
+    """what both composites take beside the photographs is tensors of the right types: an entry's first look at them"""
+    import torch
+    from . import _lib
+    _lib.check_tensors(what, [("x_lo", x_lo), ("rendered", rendered), ("mask_u8", mask_u8), ("out", out)], one_device=False,
+                       rendered=_lib.FLOATS, mask_u8=torch.uint8, out=torch.uint8)
+
+
+def _composite_operands(what, photo_u8, x_lo, rendered, mask_u8, out, detail_clamp, floor, B, h, w, window, frame=""):
+    """The operands both composites share, for B faces of a network of (h, w) and an output `window` (rows, columns), or GcfrError
+    -> the photographs, x_lo, rendered and the mask as the kernels read them, L, and the result's shape."""
+    import torch
+    from . import _lib
+    _lib.check_shape("x_lo", x_lo, (B, h, w, 3))
+    L = rendered.shape[1] if rendered.dim() == 5 else 1
+    shape = ((B, L) if rendered.dim() == 5 else (B,)) + tuple(window) + (3,)
+    _lib.check_shape("rendered", rendered, (B, 3, h, w), (B, L, 3, h, w))
+    if not 1 <= L <= FULLRES_MAX_LIGHTS:
+        raise _lib.GcfrError("%s: rendered %s: 1 <= L <= %d" % (what, tuple(rendered.shape), FULLRES_MAX_LIGHTS))
+    _lib.check_shape("mask_u8", mask_u8, (h, w), (1, h, w), (B, h, w), why=" (the uint8 skin mask at the network's resolution%s)" % frame)
+    if not float(detail_clamp) >= 1.0 or not float(floor) > 0.0:
+        raise _lib.GcfrError("%s: detail_clamp >= 1 and floor > 0; got %r, %r" % (what, detail_clamp, floor))
+    _lib.check_out(out, shape)
+    _lib.require_device(photo_u8, x_lo, rendered, mask_u8, out)
+    return (photo_u8.detach().contiguous(), x_lo.detach().contiguous(), rendered.detach().to(torch.float32).contiguous(),
+            mask_u8.contiguous().reshape(-1, h, w), L, shape)
 
 
 def ingest_photographs_device(photo_u8, scale):
@@ -172,33 +201,17 @@ def fullres_composites_device(photo_u8, x_lo, rendered, mask_u8, scale, detail_c
     if isinstance(range_sigma, bool) or not isinstance(range_sigma, (int, float)) or not float(range_sigma) > 0.0:
         raise _lib.GcfrError("%s: range_sigma > 0 (grey levels); got %r" % (what, range_sigma))
     B, h, w, s = _check_photographs(photo_u8, scale, what)
-    H, W = s * h, s * w
-    tensors = _lib.check_tensors(what, [("x_lo", x_lo), ("rendered", rendered), ("mask_u8", mask_u8), ("out", out)], one_device=False,
-                                 rendered=_lib.FLOATS, mask_u8=torch.uint8, out=torch.uint8)
-    _lib.check_shape("x_lo", x_lo, (B, h, w, 3))
-    multi = rendered.dim() == 5
-    L = rendered.shape[1] if multi else 1
-    lead = (B, L) if multi else (B,)
-    _lib.check_shape("rendered", rendered, (B, 3, h, w), (B, L, 3, h, w))
-    if not 1 <= L <= FULLRES_MAX_LIGHTS:
-        raise _lib.GcfrError("%s: rendered %s: 1 <= L <= %d" % (what, tuple(rendered.shape), FULLRES_MAX_LIGHTS))
-    _lib.check_shape("mask_u8", mask_u8, (h, w), (1, h, w), (B, h, w), why=" (the uint8 skin mask at the network's resolution)")
-    if not float(detail_clamp) >= 1.0 or not float(floor) > 0.0:
-        raise _lib.GcfrError("%s: detail_clamp >= 1 and floor > 0; got %r, %r" % (what, detail_clamp, floor))
-    _lib.check_out(out, lead + (H, W, 3))
-    _lib.require_device(photo_u8, *tensors)
-    photo, x = photo_u8.detach().contiguous(), x_lo.detach().contiguous()
-    ren = rendered.detach().to(torch.float32).contiguous()
-    m = mask_u8.contiguous().reshape(-1, h, w)
+    _check_composite_tensors(what, x_lo, rendered, mask_u8, out)
+    photo, x, ren, m, L, shape = _composite_operands(what, photo_u8, x_lo, rendered, mask_u8, out, detail_clamp, floor, B, h, w, (s * h, s * w))
     if out is not None and out.data_ptr() == photo.data_ptr():
         raise _lib.GcfrError("%s: out must not be the photographs" % what)
-    res = torch.empty(lead + (H, W, 3), dtype=torch.uint8, device=photo.device) if out is None else out
+    res = torch.empty(shape, dtype=torch.uint8, device=photo.device) if out is None else out
     if upsample == "guided":
         _lib.launch("gcfr_fullres_composites_guided_u8", photo.device, photo, x, ren, m, m.shape[0], B, L, h, w, s, float(floor),
                     float(detail_clamp), float(range_sigma), res, _lib.STREAM)
-        return res
-    _lib.launch("gcfr_fullres_composites_u8", photo.device, photo, x, ren, m, m.shape[0], B, L, h, w, s, float(floor),
-                float(detail_clamp), res, _lib.STREAM)
+    else:
+        _lib.launch("gcfr_fullres_composites_u8", photo.device, photo, x, ren, m, m.shape[0], B, L, h, w, s, float(floor),
+                    float(detail_clamp), res, _lib.STREAM)
     return res
 
 
@@ -208,12 +221,7 @@ def _check_boxes(boxes, photo_u8, h, w, what, same_size=False):
     array or a CPU tensor of integers."""
     import torch
     from . import _lib
-    _lib.check_tensors(what, [("photographs", photo_u8)], photographs=torch.uint8)
-    if photo_u8.dim() != 4 or photo_u8.shape[-1] != 3 or min(photo_u8.shape) < 1:
-        raise _lib.GcfrError("%s: photographs must be a uint8 tensor (B,Hp,Wp,3); got %s" % (what, tuple(photo_u8.shape)))
-    B, Hp, Wp, _ = photo_u8.shape
-    if Hp * Wp > 0x7fffffff or B * ((Hp * Wp + 1023) // 1024) > 0x7fffffff:
-        raise _lib.GcfrError("%s: %d photographs of %d x %d pixels do not fit the kernels' 31-bit pixel and chunk counts" % (what, B, Hp, Wp))
+    B, Hp, Wp, _ = _check_photographs(photo_u8, 1, what, boxed=True)
     if any(isinstance(n, bool) or not isinstance(n, int) or n < 1 for n in (h, w)):
         raise _lib.GcfrError("%s: the network's size (h, w) must be positive integers; got %r" % (what, (h, w)))
     if torch.is_tensor(boxes):
@@ -286,32 +294,18 @@ def fullres_box_composites_device(photo_u8, boxes, x_lo, rendered, mask_u8, deta
     what = "fullres_box_composites_device"
     if not isinstance(paste, (bool, int)) or paste not in (0, 1):
         raise _lib.GcfrError("%s: paste must be True or False; got %r" % (what, paste))
-    tensors = _lib.check_tensors(what, [("x_lo", x_lo), ("rendered", rendered), ("mask_u8", mask_u8), ("out", out)], one_device=False,
-                                 rendered=_lib.FLOATS, mask_u8=torch.uint8, out=torch.uint8)
+    _check_composite_tensors(what, x_lo, rendered, mask_u8, out)
     if x_lo.dim() != 4 or x_lo.shape[-1] != 3 or min(x_lo.shape) < 1:
         raise _lib.GcfrError("%s: x_lo must be (B,h,w,3); got %s" % (what, tuple(x_lo.shape)))
     h, w = int(x_lo.shape[1]), int(x_lo.shape[2])
     bx = _check_boxes(boxes, photo_u8, h, w, what, same_size=not paste)
     B, Hp, Wp, _ = photo_u8.shape
-    _lib.check_shape("x_lo", x_lo, (B, h, w, 3))
-    multi = rendered.dim() == 5
-    L = rendered.shape[1] if multi else 1
-    lead = (B, L) if multi else (B,)
-    _lib.check_shape("rendered", rendered, (B, 3, h, w), (B, L, 3, h, w))
-    if not 1 <= L <= FULLRES_MAX_LIGHTS:
-        raise _lib.GcfrError("%s: rendered %s: 1 <= L <= %d" % (what, tuple(rendered.shape), FULLRES_MAX_LIGHTS))
-    _lib.check_shape("mask_u8", mask_u8, (h, w), (1, h, w), (B, h, w), why=" (the uint8 skin mask at the network's resolution, in the box's frame)")
-    if not float(detail_clamp) >= 1.0 or not float(floor) > 0.0:
-        raise _lib.GcfrError("%s: detail_clamp >= 1 and floor > 0; got %r, %r" % (what, detail_clamp, floor))
     window = (Hp, Wp) if paste else (int(bx[0, 3]), int(bx[0, 2]))
-    _lib.check_out(out, lead + window + (3,))
-    _lib.require_device(photo_u8, *tensors)
-    photo, x = photo_u8.detach().contiguous(), x_lo.detach().contiguous()
-    ren = rendered.detach().to(torch.float32).contiguous()
-    m = mask_u8.contiguous().reshape(-1, h, w)
+    photo, x, ren, m, L, shape = _composite_operands(what, photo_u8, x_lo, rendered, mask_u8, out, detail_clamp, floor, B, h, w, window,
+                                                     frame=", in the box's frame")
     if out is not None and out.data_ptr() < photo.data_ptr() + photo.numel() and photo.data_ptr() < out.data_ptr() + out.numel():
         raise _lib.GcfrError("%s: out must not overlap the photographs" % what)
-    res = torch.empty(lead + window + (3,), dtype=torch.uint8, device=photo.device) if out is None else out
+    res = torch.empty(shape, dtype=torch.uint8, device=photo.device) if out is None else out
     _lib.launch("gcfr_fullres_composites_box_u8", photo.device, photo, x, ren, m, m.shape[0], B, L, Hp, Wp, _host_pointer(bx), h, w,
                 int(bool(paste)), float(floor), float(detail_clamp), res, _lib.STREAM)
     return res
