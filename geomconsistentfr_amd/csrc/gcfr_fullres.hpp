@@ -1,14 +1,20 @@
-// What the three full-resolution composites share so that they cannot drift (gcfr_fullres.hip: bilinear Up; gcfr_fullres_guided.hip:
-// joint-bilateral Up_J; gcfr_fullres_box.hip: bilinear Up over a face box).  include/gcfr.h is the statement; here is its ONE text:
-//   arithmetic   bilerp, detail_of (the quotient), fullres_value (the blend), fullres_byte (the byte)
-//   vector path  the 12-byte lane's select mask and its select-and-store (the pack / unpack pair is gcfr_reduce.hpp's), and the
-//                column offsets kP0 of a lane's four pixels
+// What the four full-resolution composites share so that they cannot drift (gcfr_fullres.hip: bilinear Up; gcfr_fullres_guided.hip:
+// joint-bilateral Up_J; gcfr_fullres_box.hip: bilinear Up over a face box; gcfr_fullres_box_guided.hip: Up_J over a face box).
+// include/gcfr.h is the statement; here is its ONE text:
+//   arithmetic   bilerp, detail_of (the quotient), fullres_value (the blend), fullres_byte (the byte), guided_range (Up_J's range
+//                kernel)
+//   vector path  the 12-byte lane's select mask and its select-and-store (the pack / unpack pair is gcfr_reduce.hpp's), the
+//                column offsets kP0 of a lane's four pixels, load_dword_any (a box starts at any byte) and PlaneF32 (a plane of
+//                `rendered` behind a buffer descriptor)
 //   scalar path  composite_pixel: the whole pixel, over an upsampler object whose one operation is up(value_at); Bilinear4 is the
-//                upsampler of both bilinear kernels, filled from up_tap<S> or from box_tap
-//   per face     FacePlanes / face_planes: the five base pointers of a workgroup's face
-//   host         the shape check, the operand check of the three composite entries, and with_scale / with_flag, which turn the
-//                run-time (s, vec) into template arguments
-// The three vector-path upsamplers and the two tap functions (up_tap<S>: shifts; box_tap: divisions) stay with their kernels.
+//                upsampler of both bilinear kernels, filled from up_tap<S> or from box_tap; Guided16 that of both guided kernels,
+//                filled from guided_tap<S> or from box_tap4
+//   per face     FacePlanes / face_planes: the five base pointers of a workgroup's face; BoxArgs: the boxes of a launch, by value;
+//                box_clamp: a photograph coordinate in a box's frame
+//   host         the shape checks, the operand check of the composite entries, the box rules (boxes_ok, box_shape, box_args), and
+//                with_scale / with_flag, which turn the run-time (s, vec) into template arguments
+// The vector-path upsamplers and the tap functions (up_tap<S>, guided_tap<S>: shifts; box_tap, box_tap4: divisions) stay with
+// their kernels.
 #pragma once
 
 #include <type_traits>
@@ -132,6 +138,64 @@ __device__ inline void composite_pixel(const Up &up, const uint8_t (&pb)[3], con
     }
 }
 
+// the range kernel's weight of one tap
+__device__ inline float guided_range(const float (&p)[3], float x0, float x1, float x2, float inv)
+{
+    const float e0 = p[0] - x0 * 255.0f, e1 = p[1] - x1 * 255.0f, e2 = p[2] - x2 * 255.0f;
+    const float d2 = (e0 * e0 + e1 * e1) + e2 * e2;
+    return 1.0f / (1.0f + d2 * inv);
+}
+
+// the joint-bilateral upsampler of one pixel (the scalar path): the 16 taps and their normalised weights, row-major; Up_J of the
+// plane whose value at low-resolution pixel t is value_at(t)
+struct Guided16 {
+    uint32_t tap[16];
+    float wn[16];
+    template <class V>
+    __device__ float operator()(V value_at) const
+    {
+        float acc = wn[0] * value_at(tap[0]);
+#pragma unroll
+        for (int t = 1; t < 16; ++t)
+            acc = acc + wn[t] * value_at(tap[t]);
+        return acc;
+    }
+};
+
+// the boxes of one launch of a box kernel, by value in its argument block
+constexpr int kBoxFaces = 32;                  // faces per launch: 4 x 32 int32 in the argument block
+
+struct BoxArgs {
+    int32_t x0[kBoxFaces], y0[kBoxFaces], bw[kBoxFaces], bh[kBoxFaces];
+};
+
+// box-relative coordinate of photograph coordinate p for a box that starts at b0 and is nb long, clamped into the box
+__device__ inline uint32_t box_clamp(int32_t p, int32_t b0, int32_t nb, bool &in)
+{
+    const int32_t r = p - b0;
+    in = r >= 0 && r < nb;
+    return (uint32_t)(r < 0 ? 0 : r < nb ? r : nb - 1);
+}
+
+// A plane of n floats (4 n < 2^32) behind a buffer descriptor: a load is the plane's uniform descriptor plus ONE 32-bit register of
+// byte offset per lane, where a flat load holds a 64-bit address per tap (48 of them per light, each advanced per light).
+struct PlaneF32 {
+    __amdgpu_buffer_rsrc_t rs;
+    __device__ PlaneF32(const float *plane, uint32_t n)
+        : rs(__builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(plane), 0, (int)(4u * n), 0x00020000)) {}
+    __device__ float at(uint32_t byte_offset) const
+    {
+        return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, (int)byte_offset, 0, 0));
+    }
+};
+
+__device__ inline uint32_t load_dword_any(const uint8_t *p)
+{
+    uint32_t v;
+    __builtin_memcpy(&v, p, 4);
+    return v;
+}
+
 inline bool fullres_scale_ok(int32_t s) { return s == 1 || s == 2 || s == 4 || s == 8; }
 
 // (B, h, w, s) -> the hi-res and the low-res pixel counts per face; false where a per-face pixel count or a chunk count does not
@@ -160,6 +224,40 @@ inline bool fullres_operands(const void *photo, const void *x_lo, const void *re
     mask_stride = mask_batch == 1 ? 0u : hw;
     lo = 1.0f / detail_clamp;
     return true;
+}
+
+// The box rules of include/gcfr.h for `n` faces; with `same` every box has the first one's size.
+inline bool boxes_ok(const int32_t *boxes, int32_t n, int32_t Hp, int32_t Wp, int32_t h, int32_t w, bool same)
+{
+    for (int32_t b = 0; b < n; ++b) {
+        const int64_t x0 = boxes[4 * b], y0 = boxes[4 * b + 1], bw = boxes[4 * b + 2], bh = boxes[4 * b + 3];
+        if (x0 < 0 || y0 < 0 || bw < w || bh < h || x0 + bw > Wp || y0 + bh > Hp || 2 * bh * h > 0x7fffffffll ||
+            2 * bw * w > 0x7fffffffll)
+            return false;
+        if (same && (bw != boxes[2] || bh != boxes[3]))
+            return false;
+    }
+    return true;
+}
+
+// (B, Hp, Wp, h, w) -> the photograph's and the network's pixel counts; false where a count does not fit 31 bits
+inline bool box_shape(int32_t B, int32_t Hp, int32_t Wp, int32_t h, int32_t w, uint32_t &HWp, uint32_t &hw)
+{
+    if (B < 1 || Hp < 1 || Wp < 1 || h < 1 || w < 1)
+        return false;
+    const uint64_t HW64 = (uint64_t)Hp * (uint64_t)Wp, hw64 = (uint64_t)h * (uint64_t)w;
+    if (HW64 > 0x7fffffffull || hw64 > 0x7fffffffull || (uint64_t)B * ((HW64 + kQuadChunk - 1) / kQuadChunk) > 0x7fffffffull)
+        return false;
+    HWp = (uint32_t)HW64, hw = (uint32_t)hw64;
+    return true;
+}
+
+inline BoxArgs box_args(const int32_t *boxes, int32_t n)
+{
+    BoxArgs a = {};
+    for (int32_t f = 0; f < n; ++f)
+        a.x0[f] = boxes[4 * f], a.y0[f] = boxes[4 * f + 1], a.bw[f] = boxes[4 * f + 2], a.bh[f] = boxes[4 * f + 3];
+    return a;
 }
 
 // f(std::integral_constant<int, S>{}) for the scale s (fullres_scale_ok), f(std::bool_constant<v>{}) for a flag: a kernel's

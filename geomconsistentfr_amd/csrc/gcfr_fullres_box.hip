@@ -20,8 +20,9 @@
 //               a Bilinear4 filled from box_tap); a pixel of the output window outside the box is the photograph's byte for every
 //               light.
 //
-// The boxes arrive in a HOST array, are validated on the host and travel BY VALUE in the kernel's argument block (BoxArgs: up to
-// kBoxFaces faces per launch; more faces are a short loop of launches): nothing is uploaded, no device scratch, capture-safe.
+// The boxes arrive in a HOST array, are validated on the host and travel BY VALUE in the kernel's argument block (BoxArgs, in
+// gcfr_fullres.hpp: up to kBoxFaces faces per launch; more faces are a short loop of launches): nothing is uploaded, no device scratch,
+// capture-safe.
 //
 // Work split of the composite (gcfr_fullres.hip's): a workgroup of 256 lanes owns kQuadChunk = 1024 consecutive pixels of ONE face's
 // output WINDOW -- the photograph (paste = 1) or the box (paste = 0); the two differ in the window's origin and size only.  A lane
@@ -41,12 +42,6 @@
 
 namespace gcfr {
 
-constexpr int kBoxFaces = 32;                  // faces per launch: 4 x 32 int32 in the argument block
-
-struct BoxArgs {
-    int32_t x0[kBoxFaces], y0[kBoxFaces], bw[kBoxFaces], bh[kBoxFaces];
-};
-
 // one axis of Up over a box: box-relative index i of a box axis of nb over a low-resolution axis of n (2 nb n < 2^31)
 __device__ inline void box_tap(uint32_t i, uint32_t n, uint32_t nb, uint32_t &i0, uint32_t &i1, float &t)
 {
@@ -57,33 +52,6 @@ __device__ inline void box_tap(uint32_t i, uint32_t n, uint32_t nb, uint32_t &i0
     const uint32_t rem = N - i0 * den;
     t = (float)((double)rem / (double)den);
     i1 = i0 + 1u < n ? i0 + 1u : n - 1u;
-}
-
-// box-relative coordinate of photograph coordinate p for a box that starts at b0 and is nb long, clamped into the box
-__device__ inline uint32_t box_clamp(int32_t p, int32_t b0, int32_t nb, bool &in)
-{
-    const int32_t r = p - b0;
-    in = r >= 0 && r < nb;
-    return (uint32_t)(r < 0 ? 0 : r < nb ? r : nb - 1);
-}
-
-// A plane of n floats (4 n < 2^32) behind a buffer descriptor: a load is the plane's uniform descriptor plus ONE 32-bit register of
-// byte offset per lane, where a flat load holds a 64-bit address per tap (48 of them per light, each advanced per light).
-struct PlaneF32 {
-    __amdgpu_buffer_rsrc_t rs;
-    __device__ PlaneF32(const float *plane, uint32_t n)
-        : rs(__builtin_amdgcn_make_buffer_rsrc(const_cast<float *>(plane), 0, (int)(4u * n), 0x00020000)) {}
-    __device__ float at(uint32_t byte_offset) const
-    {
-        return __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rs, (int)byte_offset, 0, 0));
-    }
-};
-
-__device__ inline uint32_t load_dword_any(const uint8_t *p)
-{
-    uint32_t v;
-    __builtin_memcpy(&v, p, 4);
-    return v;
 }
 
 // WW, WN: the window's width and pixel count (paste: Wp, Hp Wp; else the faces' common bw, bh bw)
@@ -244,40 +212,6 @@ __global__ __launch_bounds__(kQuadLanes) void ingest_box_kernel(const uint8_t *_
         for (int c = 0; c < 3; ++c)
             xl_b[3u * (size_t)px + c] = (float)((double)acc[c] / den);
     }
-}
-
-// The box rules of include/gcfr.h for `n` faces; with `same` every box has the first one's size.
-inline bool boxes_ok(const int32_t *boxes, int32_t n, int32_t Hp, int32_t Wp, int32_t h, int32_t w, bool same)
-{
-    for (int32_t b = 0; b < n; ++b) {
-        const int64_t x0 = boxes[4 * b], y0 = boxes[4 * b + 1], bw = boxes[4 * b + 2], bh = boxes[4 * b + 3];
-        if (x0 < 0 || y0 < 0 || bw < w || bh < h || x0 + bw > Wp || y0 + bh > Hp || 2 * bh * h > 0x7fffffffll ||
-            2 * bw * w > 0x7fffffffll)
-            return false;
-        if (same && (bw != boxes[2] || bh != boxes[3]))
-            return false;
-    }
-    return true;
-}
-
-// (B, Hp, Wp, h, w) -> the photograph's and the network's pixel counts; false where a count does not fit 31 bits
-inline bool box_shape(int32_t B, int32_t Hp, int32_t Wp, int32_t h, int32_t w, uint32_t &HWp, uint32_t &hw)
-{
-    if (B < 1 || Hp < 1 || Wp < 1 || h < 1 || w < 1)
-        return false;
-    const uint64_t HW64 = (uint64_t)Hp * (uint64_t)Wp, hw64 = (uint64_t)h * (uint64_t)w;
-    if (HW64 > 0x7fffffffull || hw64 > 0x7fffffffull || (uint64_t)B * ((HW64 + kQuadChunk - 1) / kQuadChunk) > 0x7fffffffull)
-        return false;
-    HWp = (uint32_t)HW64, hw = (uint32_t)hw64;
-    return true;
-}
-
-inline BoxArgs box_args(const int32_t *boxes, int32_t n)
-{
-    BoxArgs a = {};
-    for (int32_t f = 0; f < n; ++f)
-        a.x0[f] = boxes[4 * f], a.y0[f] = boxes[4 * f + 1], a.bw[f] = boxes[4 * f + 2], a.bh[f] = boxes[4 * f + 3];
-    return a;
 }
 
 }  // namespace gcfr

@@ -63,30 +63,6 @@ __device__ inline void guided_tap(uint32_t i, uint32_t n, uint32_t (&tap)[4], fl
     wgt[0] = (float)(2u * S - r) * q, wgt[1] = (float)(4u * S - r) * q, wgt[2] = (float)(2u * S + r) * q, wgt[3] = (float)r * q;
 }
 
-// the range kernel's weight of one tap
-__device__ inline float guided_range(const float (&p)[3], float x0, float x1, float x2, float inv)
-{
-    const float e0 = p[0] - x0 * 255.0f, e1 = p[1] - x1 * 255.0f, e2 = p[2] - x2 * 255.0f;
-    const float d2 = (e0 * e0 + e1 * e1) + e2 * e2;
-    return 1.0f / (1.0f + d2 * inv);
-}
-
-// the joint-bilateral upsampler of one pixel (the scalar path): the 16 taps and their normalised weights, row-major; Up_J of the
-// plane whose value at low-resolution pixel t is value_at(t)
-struct Guided16 {
-    uint32_t tap[16];
-    float wn[16];
-    template <class V>
-    __device__ float operator()(V value_at) const
-    {
-        float acc = wn[0] * value_at(tap[0]);
-#pragma unroll
-        for (int t = 1; t < 16; ++t)
-            acc = acc + wn[t] * value_at(tap[t]);
-        return acc;
-    }
-};
-
 template <int S, bool VEC>
 __global__ __launch_bounds__(kQuadLanes) void fullres_composites_guided_kernel(
     const uint8_t *__restrict__ photo, const float *__restrict__ x_lo, const float *__restrict__ rendered,

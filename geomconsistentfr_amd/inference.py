@@ -281,8 +281,8 @@ def relight_lights_in_photograph(model, photos_u8, boxes, mask_u8, lights, ambie
     ONE `forward_lights` pass on it, then ONE `postprocess.fullres_box_composites_device` launch for all L lights.  The network's
     size (h, w) is `mask_u8`'s; `mask_u8` and `composite_mask_u8` are in the box's frame.  `model` / `ambient` / `focal` as in
     `relight_lights`; `detail_clamp` / `floor` as in `relight_lights_fullres`, whose bytes these are when the box is the whole
-    photograph at 1, 2, 4 or 8 times the network's side.  The edge-aware upsample is not available over a box.  One
-    device-to-host copy of the result at the end."""
+    photograph at 1, 2, 4 or 8 times the network's side.  The edge-aware upsample over a box is
+    `relight_lights_in_photograph_guided`.  One device-to-host copy of the result at the end."""
     return relight_lights_in_photograph_device(model, photos_u8, boxes, mask_u8, lights, ambient, focal, device, composite_mask_u8,
                                                epoch, detail_clamp, floor, paste).cpu().numpy()
 
@@ -310,6 +310,58 @@ def relight_rig_in_photograph(model, photos_u8, boxes, mask_u8, lights, light_rg
     colour 1 the composite equals `relight_lights_in_photograph(...)[:, 0]`.  One device-to-host copy at the end."""
     return relight_rig_in_photograph_device(model, photos_u8, boxes, mask_u8, lights, light_rgb, ambient, focal, device,
                                             composite_mask_u8, epoch, detail_clamp, floor, paste).cpu().numpy()
+
+
+@torch.no_grad()
+def relight_lights_in_photograph_guided_device(model, photos_u8, boxes, mask_u8, lights, ambient: float = 0.5, focal: float = None,
+                                               device="cuda", composite_mask_u8=None, epoch: int = 200, detail_clamp: float = 4.0,
+                                               floor: float = 1.0, paste: bool = True, range_sigma: float = 20.0) -> torch.Tensor:
+    """`relight_lights_in_photograph_guided` up to the bytes ON THE DEVICE: (B,L,Hp,Wp,3) uint8 tensor (`paste=False`:
+    (B,L,bh,bw,3)), nothing copied back."""
+    _check_host_boxes(boxes)
+    return _relight_photographs(model, photos_u8, mask_u8, lights, ambient, focal, device, composite_mask_u8, epoch,
+                                lambda ph: pp.ingest_box_device(ph, boxes, _network_size(mask_u8)),
+                                lambda ph, *a: pp.fullres_box_composites_device(ph, boxes, *a, detail_clamp, floor, paste=paste,
+                                                                                upsample="guided", range_sigma=range_sigma))
+
+
+@torch.no_grad()
+def relight_lights_in_photograph_guided(model, photos_u8, boxes, mask_u8, lights, ambient: float = 0.5, focal: float = None,
+                                        device="cuda", composite_mask_u8=None, epoch: int = 200, detail_clamp: float = 4.0,
+                                        floor: float = 1.0, paste: bool = True, range_sigma: float = 20.0) -> np.ndarray:
+    """`relight_lights_in_photograph` with the EDGE-AWARE upsample over the box: the relit image, the quotient and the mask are
+    carried up by the joint-bilateral upsample guided by the photograph (`postprocess.fullres_box_composites_device(
+    upsample="guided")`; `range_sigma` in grey levels, an argument and not a tuned value), so that neither the relighting gain nor
+    the mask crosses an edge the network's resolution does not see.  Everything else is `relight_lights_in_photograph`'s; with the
+    box the whole photograph at 1, 2, 4 or 8 times the network's side these are `relight_lights_fullres(upsample="guided")`'s
+    bytes.  One device-to-host copy of the result at the end."""
+    return relight_lights_in_photograph_guided_device(model, photos_u8, boxes, mask_u8, lights, ambient, focal, device, composite_mask_u8,
+                                                      epoch, detail_clamp, floor, paste, range_sigma).cpu().numpy()
+
+
+@torch.no_grad()
+def relight_rig_in_photograph_guided_device(model, photos_u8, boxes, mask_u8, lights, light_rgb, ambient: float = 0.5, focal: float = None,
+                                            device="cuda", composite_mask_u8=None, epoch: int = 200, detail_clamp: float = 4.0,
+                                            floor: float = 1.0, paste: bool = True, range_sigma: float = 20.0) -> torch.Tensor:
+    """`relight_rig_in_photograph_guided` up to the bytes ON THE DEVICE: (B,Hp,Wp,3) uint8 tensor (`paste=False`: (B,bh,bw,3)),
+    nothing copied back."""
+    _check_host_boxes(boxes)
+    return _relight_photographs(model, photos_u8, mask_u8, lights, ambient, focal, device, composite_mask_u8, epoch,
+                                lambda ph: pp.ingest_box_device(ph, boxes, _network_size(mask_u8)),
+                                lambda ph, *a: pp.fullres_box_composites_device(ph, boxes, *a, detail_clamp, floor, paste=paste,
+                                                                                upsample="guided", range_sigma=range_sigma),
+                                light_rgb, rig=True)
+
+
+@torch.no_grad()
+def relight_rig_in_photograph_guided(model, photos_u8, boxes, mask_u8, lights, light_rgb, ambient: float = 0.5, focal: float = None,
+                                     device="cuda", composite_mask_u8=None, epoch: int = 200, detail_clamp: float = 4.0,
+                                     floor: float = 1.0, paste: bool = True, range_sigma: float = 20.0) -> np.ndarray:
+    """`relight_rig_in_photograph` with the edge-aware upsample over the box (`relight_lights_in_photograph_guided`): ONE
+    (B,Hp,Wp,3) uint8 RGB composite per photograph under the rig; with one light of colour 1 it equals
+    `relight_lights_in_photograph_guided(...)[:, 0]`.  One device-to-host copy at the end."""
+    return relight_rig_in_photograph_guided_device(model, photos_u8, boxes, mask_u8, lights, light_rgb, ambient, focal, device,
+                                                   composite_mask_u8, epoch, detail_clamp, floor, paste, range_sigma).cpu().numpy()
 
 
 def _rig_frames(x, out, cm, light_rgb_frames, transfer: bool, fix_border: bool) -> torch.Tensor:

@@ -11,7 +11,8 @@ Device path (HIP kernels of csrc/gcfr_postprocess.hip, no CPU fallback): `infere
   fullres_composites_device     the relit low-resolution images carried back onto the photograph's own pixels, uint8
   ingest_box_device             a face box of any size and position inside a larger photograph -> the network's f32 input,
                                 csrc/gcfr_fullres_box.hip
-  fullres_box_composites_device the relit images carried back onto the box's pixels: the photograph relit inside the box, uint8
+  fullres_box_composites_device the relit images carried back onto the box's pixels: the photograph relit inside the box, uint8;
+                                upsample="guided": edge-aware, csrc/gcfr_fullres_box_guided.hip
 
 Host side: the on-disk formats of load_data() (T8:545-556).  The numpy statements of the script lines these kernels
 implement live in oracle/postprocess_statements.py (test infrastructure, pinned to the reference's own main() by
@@ -175,6 +176,15 @@ def ingest_photographs_device(photo_u8, scale):
 FULLRES_UPSAMPLES = ("bilinear", "guided")
 
 
+def _check_upsample(what, upsample, range_sigma):
+    """the two keywords of both composite entries, or GcfrError: an entry's first check, with either upsample"""
+    from . import _lib
+    if upsample not in FULLRES_UPSAMPLES:
+        raise _lib.GcfrError("%s: upsample must be one of %s; got %r" % (what, FULLRES_UPSAMPLES, upsample))
+    if isinstance(range_sigma, bool) or not isinstance(range_sigma, (int, float)) or not float(range_sigma) > 0.0:
+        raise _lib.GcfrError("%s: range_sigma > 0 (grey levels); got %r" % (what, range_sigma))
+
+
 def fullres_composites_device(photo_u8, x_lo, rendered, mask_u8, scale, detail_clamp=4.0, floor=1.0, out=None, upsample="bilinear",
                               range_sigma=20.0):
     """The relit low-resolution `rendered` of ONE pass carried back onto the photographs' own pixels, as uint8 on the device:
@@ -196,10 +206,7 @@ def fullres_composites_device(photo_u8, x_lo, rendered, mask_u8, scale, detail_c
     import torch
     from . import _lib
     what = "fullres_composites_device"
-    if upsample not in FULLRES_UPSAMPLES:
-        raise _lib.GcfrError("%s: upsample must be one of %s; got %r" % (what, FULLRES_UPSAMPLES, upsample))
-    if isinstance(range_sigma, bool) or not isinstance(range_sigma, (int, float)) or not float(range_sigma) > 0.0:
-        raise _lib.GcfrError("%s: range_sigma > 0 (grey levels); got %r" % (what, range_sigma))
+    _check_upsample(what, upsample, range_sigma)
     B, h, w, s = _check_photographs(photo_u8, scale, what)
     _check_composite_tensors(what, x_lo, rendered, mask_u8, out)
     photo, x, ren, m, L, shape = _composite_operands(what, photo_u8, x_lo, rendered, mask_u8, out, detail_clamp, floor, B, h, w, (s * h, s * w))
@@ -277,7 +284,8 @@ def ingest_box_device(photo_u8, boxes, size):
     return x_lo
 
 
-def fullres_box_composites_device(photo_u8, boxes, x_lo, rendered, mask_u8, detail_clamp=4.0, floor=1.0, paste=True, out=None):
+def fullres_box_composites_device(photo_u8, boxes, x_lo, rendered, mask_u8, detail_clamp=4.0, floor=1.0, paste=True, out=None,
+                                  upsample="bilinear", range_sigma=20.0):
     """`fullres_composites_device` for a FACE BOX inside each photograph: photo_u8 (B,Hp,Wp,3) uint8 of any size; `boxes` host
     integers (x0, y0, bw, bh) as in `ingest_box_device`; x_lo (B,h,w,3) f32, the network's input (`ingest_box_device`); rendered
     (B,L,3,h,w) or (B,3,h,w); mask_u8 (1|B,h,w) or (h,w) uint8, the compositing mask at the network's resolution IN THE BOX'S
@@ -287,11 +295,15 @@ def fullres_box_composites_device(photo_u8, boxes, x_lo, rendered, mask_u8, deta
     the box the whole photograph at 1, 2, 4 or 8 times the network's side, that entry's bytes.  ONE launch per 32 faces for all L
     lights; the boxes travel in the launch's arguments, nothing is uploaded.  `rendered` is the only operand that may be non-f32
     on entry.  `out`: a contiguous uint8 buffer of the result's shape that is written and returned; it must not overlap the
-    photographs.  NOT DIFFERENTIABLE.  No host synchronisation; a malformed input raises GcfrError before anything is loaded or
-    launched."""
+    photographs.  `upsample` / `range_sigma` as in `fullres_composites_device`: "bilinear" (the default) is the launch described
+    above; "guided" replaces Up in all three places by the edge-aware joint-bilateral upsample taken over the box
+    (csrc/gcfr_fullres_box_guided.hip; include/gcfr.h states it), with that entry's bytes when the box is the whole photograph at
+    1, 2, 4 or 8 times the network's side.  NOT DIFFERENTIABLE.  No host synchronisation; a malformed input raises GcfrError before
+    anything is loaded or launched."""
     import torch
     from . import _lib
     what = "fullres_box_composites_device"
+    _check_upsample(what, upsample, range_sigma)
     if not isinstance(paste, (bool, int)) or paste not in (0, 1):
         raise _lib.GcfrError("%s: paste must be True or False; got %r" % (what, paste))
     _check_composite_tensors(what, x_lo, rendered, mask_u8, out)
@@ -306,8 +318,12 @@ def fullres_box_composites_device(photo_u8, boxes, x_lo, rendered, mask_u8, deta
     if out is not None and out.data_ptr() < photo.data_ptr() + photo.numel() and photo.data_ptr() < out.data_ptr() + out.numel():
         raise _lib.GcfrError("%s: out must not overlap the photographs" % what)
     res = torch.empty(shape, dtype=torch.uint8, device=photo.device) if out is None else out
-    _lib.launch("gcfr_fullres_composites_box_u8", photo.device, photo, x, ren, m, m.shape[0], B, L, Hp, Wp, _host_pointer(bx), h, w,
-                int(bool(paste)), float(floor), float(detail_clamp), res, _lib.STREAM)
+    if upsample == "guided":
+        _lib.launch("gcfr_fullres_composites_box_guided_u8", photo.device, photo, x, ren, m, m.shape[0], B, L, Hp, Wp, _host_pointer(bx),
+                    h, w, int(bool(paste)), float(floor), float(detail_clamp), float(range_sigma), res, _lib.STREAM)
+    else:
+        _lib.launch("gcfr_fullres_composites_box_u8", photo.device, photo, x, ren, m, m.shape[0], B, L, Hp, Wp, _host_pointer(bx), h, w,
+                    int(bool(paste)), float(floor), float(detail_clamp), res, _lib.STREAM)
     return res
 
 

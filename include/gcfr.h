@@ -731,6 +731,45 @@ int gcfr_fullres_composites_box_u8(const uint8_t *photo_u8, const float *x_lo, c
                                    int32_t mask_batch, int32_t B, int32_t L, int32_t Hp, int32_t Wp, const int32_t *boxes, int32_t h,
                                    int32_t w, int32_t paste, float floor, float detail_clamp, uint8_t *out_u8, void *stream);
 
+/*
+ * The box composite with the EDGE-AWARE upsample Up_J of gcfr_fullres_composites_guided_u8 in place of the bilinear Up
+ * (csrc/gcfr_fullres_box_guided.hip): the guided upsample over a face box of any integer size and position.  Operands, layouts, box
+ * rules and `paste` are exactly gcfr_fullres_composites_box_u8's, plus `range_sigma` (grey levels, > 0, +inf allowed).  Every
+ * operation is one separately rounded IEEE f32 operation unless marked otherwise; the divisions are correctly rounded.
+ *   Taps, per axis with box-relative index y, box extent b and low-resolution extent n.  The integers are Up-over-the-box's:
+ *            N = max((2y+1) n - b, 0), y0 = N div 2b, rem = N - y0 2b.  The four taps are clamp(y0 - 1 + j, 0, n - 1), j = 0..3.
+ *            Their weights are the integers (2b - rem, 4b - rem, 2b + rem, rem) over 4b, each formed as
+ *            (float)((double)k / (double)(4b)) with one rounding (sy[j], sx[i]): a tent of radius two low-resolution pixels about
+ *            the pixel's half-pixel centre.  The four integers sum to 8b.  A tap replicated at a border keeps its own weight.
+ *            4b < 2^32 follows from the box rule 2 b n < 2^31.  At b = s n the weights are the exact k / (4s) of
+ *            gcfr_fullres_composites_guided_u8.
+ *   Weights, Up_J and the composite are gcfr_fullres_composites_guided_u8's, unchanged in formula and order.  p is the
+ *            photograph's pixel inside the box; for tap (j, i) at low-resolution pixel q, g[c] = x_lo[q, c] 255.0f:
+ *              e[c] = p[c] - g[c];  d2 = (e[0] e[0] + e[1] e[1]) + e[2] e[2];  k = 1.0f / (1.0f + d2 inv)
+ *              wt = (sy[j] sx[i]) k;  den = the sum of the 16 wt, row-major (j outer, i inner), starting from wt[0][0]
+ *              rcp = 1.0f / den;  wn = wt rcp
+ *            with inv = 1.0f / (range_sigma range_sigma) formed once on the host in f32.  The product sy[j] sx[i] is a ROUNDED f32
+ *            product here (it is exact only where both weights are: at b = s n); with range_sigma = +inf, |den - 4| <= 72 x 2^-24.
+ *            Up_J(a) = the sum over the 16 taps, row-major, of wn[j][i] a[tap], the first product starting the sum; all 16 taps
+ *            are always read.  Inside the box:
+ *              xl = Up_J(x_lo[..., c]) 255.0f;  d = min(max(p / max(xl, floor), 1.0f / detail_clamp), detail_clamp)
+ *              m = Up_J((float)mask_u8 / 255.0f);  r = Up_J(rendered[b,l,c]) 255.0f;  v = p + m (r d - p)
+ *              byte = m > 0 ? saturate(rint((double)v)) : photo_u8
+ *            through the same device functions as the three entries above.  A pixel of the output window outside the box is the
+ *            photograph's byte, for every light.  mask_u8 stays low-resolution, in the box's frame.
+ *   Anchor, with no tolerance: with the box the whole photograph and bh = s h, bw = s w, s in {1, 2, 4, 8}, the bytes are those of
+ *            gcfr_fullres_composites_guided_u8.  The consequences stated there (identity, NaNs) hold here over the box.
+ * Refusals: gcfr_fullres_composites_box_u8's, and range_sigma <= 0 or a NaN; GCFR_ERR_INVALID_ARGUMENT before any launch.  32 faces
+ * per launch with the boxes by value; allocates nothing, never synchronises, may be captured into a graph.  Bit-equal to the numpy
+ * restatement (tests/fullres_box_guided_emulation.py).  Three dwords per four pixels on gcfr_fullres_composites_box_u8's
+ * conditions; one element at a time otherwise (same results).  The taps, the weights, d and m are formed once per pixel; per light a
+ * pixel costs 3 x 16 loads, products and sums, the blend and the quantisation.
+ */
+int gcfr_fullres_composites_box_guided_u8(const uint8_t *photo_u8, const float *x_lo, const float *rendered, const uint8_t *mask_u8,
+                                          int32_t mask_batch, int32_t B, int32_t L, int32_t Hp, int32_t Wp, const int32_t *boxes,
+                                          int32_t h, int32_t w, int32_t paste, float floor, float detail_clamp, float range_sigma,
+                                          uint8_t *out_u8, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Environment-map lighting: a lat-long radiance map integrated into the `rgb` (colour x weight per light) of the light-rig stage
  * above (csrc/gcfr_environment.hip).  Every texel belongs to the light direction nearest to it; a light's rgb is the
