@@ -83,19 +83,34 @@ class RelightDataset:
         return out
 
 
-def _u8_on_device(what, *tensors):
-    if any(t.dtype != torch.uint8 for t in tensors):
-        raise _lib.GcfrError("%s: uint8 tensors; got %s" % (what, ", ".join(str(t.dtype) for t in tensors)))
-    _lib.require_device(*tensors)
+MAX_METRIC_FACES = 65535      # gcfr_masked_metrics_u8 puts the face on the grid's y axis (include/gcfr.h)
+
+
+def _u8(what, named):
+    """the (name, tensor) pairs of `named` are uint8 tensors on one device: an entry's first look at them"""
+    _lib.check_tensors(what, named, **{n: torch.uint8 for n, _ in named})
+
+
+def _faces(what, name, t):
+    """-> (B, H, W) of `t`, a (B,H,W,3) tensor with no empty axis, or GcfrError"""
+    if t.dim() != 4 or t.shape[3] != 3 or min(t.shape) < 1:
+        raise _lib.GcfrError("%s: %s must be (B,H,W,3) with B, H, W >= 1; got %s" % (what, name, tuple(t.shape)))
+    return tuple(int(n) for n in t.shape[:3])
 
 
 def assemble_batch(images_u8: torch.Tensor, depth_mask_u8: torch.Tensor, face_mask_u8: torch.Tensor,
                    albedo_u8: torch.Tensor) -> Dict[str, torch.Tensor]:
     """uint8 device tensors (B,H,W,3), (B,H,W) x 3 -> {images (B,H,W,3), masks, masks_fill, albedo (B,H,W,1)} f32, with the
-    arithmetic of T8:550-556 and :610-615 (`gcfr_assemble_batch_u8`)."""
-    _u8_on_device("assemble_batch", images_u8, depth_mask_u8, face_mask_u8, albedo_u8)
+    arithmetic of T8:550-556 and :610-615 (`gcfr_assemble_batch_u8`).  A malformed input raises GcfrError before anything is
+    loaded or launched: the kernel reads B H W bytes of each of the three planes, whatever their own shapes."""
+    what = "assemble_batch"
+    planes = [("depth_mask_u8", depth_mask_u8), ("face_mask_u8", face_mask_u8), ("albedo_u8", albedo_u8)]
+    _u8(what, [("images_u8", images_u8)] + planes)
+    B, H, W = _faces(what, "images_u8", images_u8)
+    for n, t in planes:
+        _lib.check_shape("%s: %s" % (what, n), t, (B, H, W), why=" for images_u8 %s" % (tuple(images_u8.shape),))
+    _lib.require_device(images_u8, depth_mask_u8, face_mask_u8, albedo_u8)
     x, dm, fm, al = (t.contiguous() for t in (images_u8, depth_mask_u8, face_mask_u8, albedo_u8))
-    B, H, W, _ = x.shape
     f32 = dict(dtype=torch.float32, device=x.device)
     images = torch.empty((B, H, W, 3), **f32)
     masks, fill, albedo = (torch.empty((B, H, W, 1), **f32) for _ in range(3))
@@ -105,11 +120,20 @@ def assemble_batch(images_u8: torch.Tensor, depth_mask_u8: torch.Tensor, face_ma
 
 def masked_metrics(recon_u8: torch.Tensor, gt_u8: torch.Tensor, mask_u8: torch.Tensor):
     """MSE_MP.m:24 and DSSIM_MP_RGB.m:24-26 for B image pairs on the device: recon_u8, gt_u8 (B,H,W,3) uint8 RGB,
-    mask_u8 (B|1,H,W) or (H,W) uint8.  Returns (mse (B,), dssim (B,)) float64 device tensors (`gcfr_masked_metrics_u8`;
-    DSSIM follows MATLAB ssim()'s documented defaults -- unpinned, see include/gcfr.h)."""
-    _u8_on_device("masked_metrics", recon_u8, gt_u8, mask_u8)
+    mask_u8 (B|1,H,W) or (H,W) uint8; 1 <= B <= 65535.  Returns (mse (B,), dssim (B,)) float64 device tensors
+    (`gcfr_masked_metrics_u8`; DSSIM follows MATLAB ssim()'s documented defaults -- unpinned, see include/gcfr.h).  A face whose
+    mask is all zero gets NaN for both (0/0, as in MATLAB).  A malformed input raises GcfrError before anything is loaded or
+    launched."""
+    what = "masked_metrics"
+    _u8(what, [("recon_u8", recon_u8), ("gt_u8", gt_u8), ("mask_u8", mask_u8)])
+    B, H, W = _faces(what, "recon_u8", recon_u8)
+    of = " for recon_u8 %s" % (tuple(recon_u8.shape),)
+    _lib.check_shape("%s: gt_u8" % what, gt_u8, (B, H, W, 3), why=of)
+    _lib.check_shape("%s: mask_u8" % what, mask_u8, (H, W), (1, H, W), (B, H, W), why=of)
+    if B > MAX_METRIC_FACES:
+        raise _lib.GcfrError("%s: recon_u8 %s: 1 <= B <= %d image pairs in one call" % (what, tuple(recon_u8.shape), MAX_METRIC_FACES))
+    _lib.require_device(recon_u8, gt_u8, mask_u8)
     r, g = recon_u8.contiguous(), gt_u8.contiguous()
-    B, H, W, _ = r.shape
     m = mask_u8.contiguous().reshape(-1, H, W)
     ws_bytes = int(_lib.load().gcfr_masked_metrics_workspace_bytes(B, H, W))
     ws = torch.empty(ws_bytes // 8, dtype=torch.float64, device=r.device)
