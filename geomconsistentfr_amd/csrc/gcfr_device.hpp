@@ -123,9 +123,13 @@ __device__ inline float norm3_torch(float a, float b, float c)
 // census: epilogue: shading: shadow transfer (expf, division; T8:517)
 // T8:517: w = 1 - 4 e^-d / (1 + e^-d)^2   (== tanh^2(d/2)); evaluated as written, in f32.
 // (Round 5: e^-d by v_exp_f32 on a product carried in two floats -- t = x log2(e) as hi + lo, 2^hi from the hardware, the lo part as a
-//  first-order correction: ~1.5 ulp for every d, where the one-multiply __expf loses |t| ulp; libm's expf plus an IEEE division were 29
-//  instructions per pixel, this is 13.  The quotient by a Newton-refined reciprocal of (1 + e)^2 in [1, 4]: within an ulp of the
-//  division's.  w is compared under tolerances: <= 1e-6 against the C oracle, 2e-5 against the golden cases, gate 1e-4.)
+//  first-order correction, where the one-multiply __expf loses |t| ulp; libm's expf plus an IEEE division were 29 instructions per
+//  pixel, this is 13.  The quotient by a Newton-refined reciprocal of (1 + e)^2 in [1, 4].  w is compared under tolerances: <= 1e-6
+//  against the C oracle, 2e-5 against the golden cases, gate 1e-4.
+//  Measured on an MI355X, 2026-10-20, over every float d of [0, 200] and 4096 per binade above (tests/test_gpu_device_primitives.py,
+//  profiles/device_primitives.md): e^-d within 1.27 f32 ulp of the f64 value wherever that is a normal f32 (v_exp_f32 alone: 0.79; without
+//  the lo part: 64), a denormal-range result flushed or within 2^-126; w within 1.8e-7 (three half-ulps of 1) of the oracle's chain in
+//  IEEE f32, within 1.94e-7 of tanh^2(d/2) where the chain itself is within 1.63e-7; w(0) == 0, -1e-6 <= w <= 1, w == 1 from d = 40 on.)
 __device__ inline float exp_neg(float d)  // e^-d, d >= 0 (NaN in, NaN out; large d: 0)
 {
     const float x = -((d > 200.0f) ? 200.0f : d);  // (e^-200 is 0 in f32; keeps +inf out of the hi / lo split; NaN stays NaN)
@@ -158,9 +162,13 @@ struct Shaded {
 // the forward's -- a gradient flowed through a term the forward had clamped to zero).
 // 1 / max(|v|, 1e-12) of a 3-vector (F.normalize's denominator, T8:364-365): v_rsq_f32 (1 ulp) and one Newton step instead of
 // an IEEE square root (19 instructions) and, per component, an IEEE division (11): round 5's census counted 110 VALU
-// instructions per pixel for the two normalisations of lambert_dot(), a seventh of the march's per-tile fixed cost.  The unit
-// vector's components come out within ~1 ulp of the exactly rounded quotient (the reference's own sqrt-then-divide is within ~1
-// ulp as well); shading is compared under tolerances (full_shading <= 1e-5 against the golden cases), never bit for bit.
+// instructions per pixel for the two normalisations of lambert_dot(), a seventh of the march's per-tile fixed cost.  Measured
+// on an MI355X, 2026-10-20 (tests/test_gpu_device_primitives.py, profiles/device_primitives.md): the reciprocal norm is within
+// 1.22e-7 relative (2.04 2^-24, one f32 ulp at worst) of 1 / sqrt(s2) in f64, over every (0, 0, c) and 2^24 vectors of length
+// 1e-13 ... 1e18 -- v_rsq_f32 alone measures 9.4e-8 there, so the Newton step buys no accuracy on this chip; it is what turns
+// s2 = +inf into NaN -- and lambert_dot() within 3.0e-7 of the f64 dot product, with the exact sign wherever |dot| >= 1e-4 (the
+// window of the backward kernels' kink rule).  Shading is compared under tolerances (full_shading <= 1e-5 against the golden
+// cases), never bit for bit.
 // (|v|^2 overflowing to +inf -- |v| > 1.8e19 -- gives NaN where sqrt-then-divide gives 0; no light or normal is that long.)
 __device__ inline float inv_norm3_clamped(float a, float b, float c)
 {
@@ -222,8 +230,9 @@ struct Grad3 {
     double du[3], dv[3];
 };
 
-// 1/x to full f64 precision (<= 1 ulp) in 5 instructions instead of the ~17 of an IEEE division: v_rcp_f64 seed (about
-// 2^-26) and two Newton steps.  Normals (forward and backward) and backward kernels only -- quantities compared under
+// 1/x to full f64 precision in 5 instructions instead of the ~17 of an IEEE division: v_rcp_f64 seed (about 2^-26) and two
+// Newton steps -- measured on an MI355X, 2026-10-20, over +-2^-200 ... 2^200 (tests/test_gpu_device_primitives.py): the IEEE
+// quotient for all but 61 inputs in a million, the double next to it for those; with one step up to 14 ulp.  Normals (forward and backward) and backward kernels only -- quantities compared under
 // tolerances, never bit for bit -- and only for normal, non-zero x (norms clamped to >= 1e-12, distances).
 __device__ inline double fast_rcp64(double x)
 {
@@ -233,11 +242,13 @@ __device__ inline double fast_rcp64(double x)
     return r;
 }
 
-// sqrt(x) to ~1 ulp of f64 in 8 instructions instead of the ~30 of the IEEE routine: v_rsq_f64 seed and two coupled
-// Newton steps (Goldschmidt).  Normals and backward kernels only, x normal and > 0 (squared norms with a floor).
+// sqrt(x) in 8 instructions instead of the ~30 of the IEEE routine: v_rsq_f64 seed and two coupled Newton steps (Goldschmidt).
+// Normals and backward kernels only, x normal and > 0 (squared norms with a floor).  Measured on an MI355X, 2026-10-20, over
+// 2^-200 ... 2^200 (tests/test_gpu_device_primitives.py): the correctly rounded value for 80 % of the inputs, the double next to it
+// for the rest (|error| <= 1.5 ulp; 0.4 % of the inputs are beyond 1 ulp of the true value).
 __device__ inline double fast_sqrt64(double x)
 {
-    double y = __builtin_amdgcn_rsq(x);       // ~2^-26
+    double y = __builtin_amdgcn_rsq(x);       // ~2^-24.6 (measured through fast_rsqrt64's former single Newton step)
     double g = x * y, h = 0.5 * y;
     double e = __builtin_fma(-h, g, 0.5);
     g = __builtin_fma(g, e, g);
@@ -296,12 +307,16 @@ __device__ inline Grad3 point_gradients(const NormalsArgs &a, const float *z, in
     return g;
 }
 
-// 1/sqrt(x) to ~1 ulp of f64 in 5 instructions: v_rsq_f64 seed (about 2^-26) and one Newton step.  x normal and > 0.
+// 1/sqrt(x) of f64 in 6 instructions: v_rsq_f64 seed and one third-order step (the series of (1 - r)^-1/2 up to r^2, r = 1 - x y^2).
+// x normal and > 0.  The seed measures about 2^-24.6, not 2^-26: the single Newton step that stood here until 2026-10-20 came out
+// up to 20 ulp from 1.0 / sqrt(x) (9 % of the inputs beyond 2 ulp) under a comment that said ~1 ulp.  Measured now, MI355X,
+// 2026-10-20, over 2^-200 ... 2^200 (tests/test_gpu_device_primitives.py, profiles/device_primitives.md): at most 2 doubles from the
+// IEEE 1.0 / sqrt(x) (0.12 % of the inputs; 72 % equal), and within 1 ulp of the true value for every pair checked exactly.
 __device__ inline double fast_rsqrt64(double x)
 {
     const double y = __builtin_amdgcn_rsq(x);
-    const double g = x * y, h = 0.5 * y;
-    return __builtin_fma(y, __builtin_fma(-h, g, 0.5), y);
+    const double r = __builtin_fma(-(x * y), y, 1.0);  // 1 - x y^2
+    return __builtin_fma(y * r, __builtin_fma(0.375, r, 0.5), y);  // y (1 - r)^-1/2 = y (1 + r/2 + 3 r^2/8 + ...)
 }
 
 // Unit normal of pixel (r,c) as f32, y negated if requested (T8:353-354) -- shared by normals_fwd_kernel, the march

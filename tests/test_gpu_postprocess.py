@@ -167,3 +167,27 @@ def test_device_functions_have_no_cpu_path():
         pp.inference_images_device(torch.zeros(1, 8, 8, 3), torch.zeros(1, 3, 8, 8), torch.ones(1, 8, 8, dtype=torch.uint8))
     with pytest.raises(GcfrError):
         pp.fix_border_artifacts_device(torch.zeros(1, 8, 8, 3, dtype=torch.uint8), torch.ones(8, 8, dtype=torch.uint8))
+
+
+@pytest.mark.parametrize("mask_f32", [False, True])
+def test_byte_lattice_every_mask_byte_on_the_half_way_points(mask_f32):
+    """Every one of the 256 mask bytes (a resized face mask takes them all), and under each the values at which every plane's
+    expression comes to k + 0.5 or one f32 step beside it (tests/device_primitives_reference.py `byte_lattice`), plus a NaN, a
+    +inf and a negative rendered value under mask 255: byte for byte the scripts' statements.  A mask formed as
+    mk * (1 / 255.0f) changes 13 % of these bytes in the f32 mode (tests/test_device_primitives_host.py)."""
+    import device_primitives_reference as ref
+    from geomconsistentfr_amd import postprocess as pp
+    lat = ref.byte_lattice(mask_f32)
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    got = pp.inference_images_device(t(lat["input"][None]), t(lat["rendered"][None]), t(lat["mask_u8"]), albedo=t(lat["albedo"][None]),
+                                     depth=t(lat["depth"][None]), shadow_mask_weights=t(lat["shadow"][None]),
+                                     final_shading=t(lat["shading"][None]), surface_normals=t(lat["normals"][None]), mask_f32=mask_f32)
+    torch.cuda.synchronize()
+    want = ref.lattice_expected(lat, mask_f32)
+    assert set(got) == set(ref.PLANES) and ref.lattice_cases(lat) > 600000
+    for k in ref.PLANES:
+        g = got[k][0].cpu().numpy()
+        print("%s: %d of %d lattice bytes differ" % (k, int(((g != want[k]) & lat["kept"][k]).sum()), int(lat["kept"][k].sum())))
+    for k in ref.PLANES:
+        np.testing.assert_array_equal(got[k][0].cpu().numpy(), want[k], err_msg=k)
+    assert list(got["rendered_image"][0, 255, 253:, 0].cpu().numpy()) == [0, 255, 0]     # NaN, +inf, negative

@@ -221,3 +221,29 @@ def test_one_white_light_and_one_frame_is_the_many_lights_composite():
     want = pp.inference_images_device(x, out[5], m)["rendered_image"]             # (B,1,H,W,3): relight_lights' composite path
     got = rig_frames_u8(out[8], out[0], x, m, torch.ones(1, 1, 1, 3, device=DEV))
     assert tuple(got.shape) == (B, 1, S, S, 3) and torch.equal(got, want) and got.float().std() > 10
+
+
+@pytest.mark.parametrize("mask_f32", [False, True])
+def test_byte_lattice_every_mask_byte_on_the_half_way_points(mask_f32):
+    """One white light, one frame, final = 1: the frame's rendered value IS the albedo plane, which carries the composite's
+    half-way lattice (tests/device_primitives_reference.py `byte_lattice`: every mask byte, 255 r m at k + 0.5 or one f32 step
+    beside it; a NaN, a +inf, a negative value under mask 255) -- byte for byte the statement, and the image kernel's bytes."""
+    import device_primitives_reference as ref
+    from geomconsistentfr_amd import postprocess as pp
+    from geomconsistentfr_amd import rig_frames_u8
+    lat = ref.byte_lattice(mask_f32)
+    H = W = ref.SIDE
+    arrays = (np.ones((1, 1, H, W), np.float32), lat["rendered"][None], lat["input"][None], lat["mask_u8"][None],
+              np.ones((1, 1, 1, 3), np.float32))
+    t = [_dev(a) for a in arrays]
+    got = rig_frames_u8(*t, mask_f32=mask_f32)
+    g = got.cpu().numpy()
+    want = emu.frames(*arrays, mask_f32)
+    assert g.shape == (1, 1, H, W, 3)
+    kept = lat["kept"]["rendered_image"]
+    print("lattice bytes that differ from the statement: %d of %d" % (int(((g[0, 0] != want[0, 0]) & kept).sum()), int(kept.sum())))
+    np.testing.assert_array_equal(g, want)
+    np.testing.assert_array_equal(g[0, 0], ref.lattice_expected(lat, mask_f32)["rendered_image"])
+    image = pp.inference_images_device(t[2], t[1], t[3], mask_f32=mask_f32)["rendered_image"]
+    assert torch.equal(got[0], image)
+    assert list(g[0, 0, 255, 253:, 0]) == [0, 255, 0]                                     # NaN, +inf, negative
