@@ -15,6 +15,8 @@
 //                with_scale / with_flag, which turn the run-time (s, vec) into template arguments
 // The vector-path upsamplers and the tap functions (up_tap<S>, guided_tap<S>: shifts; box_tap, box_tap4: divisions) stay with
 // their kernels.
+// gcfr_fullres_anybox.hip (a box smaller than the network's input on either axis) is a fifth user: the same arithmetic, vector-path
+// pieces, composite_pixel (over its own carrier, AnyCarrier) and per-face pieces, and the relaxed box rules anyboxes_ok below.
 #pragma once
 
 #include <type_traits>
@@ -233,6 +235,21 @@ inline bool boxes_ok(const int32_t *boxes, int32_t n, int32_t Hp, int32_t Wp, in
         const int64_t x0 = boxes[4 * b], y0 = boxes[4 * b + 1], bw = boxes[4 * b + 2], bh = boxes[4 * b + 3];
         if (x0 < 0 || y0 < 0 || bw < w || bh < h || x0 + bw > Wp || y0 + bh > Hp || 2 * bh * h > 0x7fffffffll ||
             2 * bw * w > 0x7fffffffll)
+            return false;
+        if (same && (bw != boxes[2] || bh != boxes[3]))
+            return false;
+    }
+    return true;
+}
+
+// The relaxed box rules of include/gcfr.h (gcfr_fullres_anybox.hip): boxes_ok with `bw >= w, bh >= h` replaced by `bw, bh >= 1 and
+// 8 bw >= w, 8 bh >= h`.
+inline bool anyboxes_ok(const int32_t *boxes, int32_t n, int32_t Hp, int32_t Wp, int32_t h, int32_t w, bool same)
+{
+    for (int32_t b = 0; b < n; ++b) {
+        const int64_t x0 = boxes[4 * b], y0 = boxes[4 * b + 1], bw = boxes[4 * b + 2], bh = boxes[4 * b + 3];
+        if (x0 < 0 || y0 < 0 || bw < 1 || bh < 1 || 8 * bw < w || 8 * bh < h || x0 + bw > Wp || y0 + bh > Hp ||
+            2 * bh * h > 0x7fffffffll || 2 * bw * w > 0x7fffffffll)
             return false;
         if (same && (bw != boxes[2] || bh != boxes[3]))
             return false;

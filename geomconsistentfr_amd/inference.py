@@ -364,6 +364,57 @@ def relight_rig_in_photograph_guided(model, photos_u8, boxes, mask_u8, lights, l
                                                    composite_mask_u8, epoch, detail_clamp, floor, paste, range_sigma).cpu().numpy()
 
 
+@torch.no_grad()
+def relight_lights_in_photograph_anybox_device(model, photos_u8, boxes, mask_u8, lights, ambient: float = 0.5, focal: float = None,
+                                               device="cuda", composite_mask_u8=None, epoch: int = 200, detail_clamp: float = 4.0,
+                                               floor: float = 1.0, paste: bool = True) -> torch.Tensor:
+    """`relight_lights_in_photograph_anybox` up to the bytes ON THE DEVICE: (B,L,Hp,Wp,3) uint8 tensor (`paste=False`:
+    (B,L,bh,bw,3)), nothing copied back."""
+    _check_host_boxes(boxes)
+    return _relight_photographs(model, photos_u8, mask_u8, lights, ambient, focal, device, composite_mask_u8, epoch,
+                                lambda ph: pp.ingest_anybox_device(ph, boxes, _network_size(mask_u8)),
+                                lambda ph, *a: pp.fullres_anybox_composites_device(ph, boxes, *a, detail_clamp, floor, paste=paste))
+
+
+@torch.no_grad()
+def relight_lights_in_photograph_anybox(model, photos_u8, boxes, mask_u8, lights, ambient: float = 0.5, focal: float = None,
+                                        device="cuda", composite_mask_u8=None, epoch: int = 200, detail_clamp: float = 4.0,
+                                        floor: float = 1.0, paste: bool = True) -> np.ndarray:
+    """`relight_lights_in_photograph` for face boxes of ANY size: a box may be smaller than the network's input on either axis, down
+    to an eighth of it (bw, bh >= 1, 8 bw >= w, 8 bh >= h) -- the face in a group photograph or a webcam frame.  The same three
+    steps with `postprocess.ingest_anybox_device` (a short axis is magnified bilinearly, in integers) and ONE
+    `postprocess.fullres_anybox_composites_device` launch per 32 faces (a short axis receives the exact area mean of the network
+    pixels a box pixel covers); large, small and mixed boxes may share a call.  Everything else, `paste` included, is
+    `relight_lights_in_photograph`'s, and so are the bytes when no box is smaller than the network's input.  One device-to-host
+    copy of the result at the end."""
+    return relight_lights_in_photograph_anybox_device(model, photos_u8, boxes, mask_u8, lights, ambient, focal, device, composite_mask_u8,
+                                                      epoch, detail_clamp, floor, paste).cpu().numpy()
+
+
+@torch.no_grad()
+def relight_rig_in_photograph_anybox_device(model, photos_u8, boxes, mask_u8, lights, light_rgb, ambient: float = 0.5, focal: float = None,
+                                            device="cuda", composite_mask_u8=None, epoch: int = 200, detail_clamp: float = 4.0,
+                                            floor: float = 1.0, paste: bool = True) -> torch.Tensor:
+    """`relight_rig_in_photograph_anybox` up to the bytes ON THE DEVICE: (B,Hp,Wp,3) uint8 tensor (`paste=False`: (B,bh,bw,3)),
+    nothing copied back."""
+    _check_host_boxes(boxes)
+    return _relight_photographs(model, photos_u8, mask_u8, lights, ambient, focal, device, composite_mask_u8, epoch,
+                                lambda ph: pp.ingest_anybox_device(ph, boxes, _network_size(mask_u8)),
+                                lambda ph, *a: pp.fullres_anybox_composites_device(ph, boxes, *a, detail_clamp, floor, paste=paste),
+                                light_rgb, rig=True)
+
+
+@torch.no_grad()
+def relight_rig_in_photograph_anybox(model, photos_u8, boxes, mask_u8, lights, light_rgb, ambient: float = 0.5, focal: float = None,
+                                     device="cuda", composite_mask_u8=None, epoch: int = 200, detail_clamp: float = 4.0,
+                                     floor: float = 1.0, paste: bool = True) -> np.ndarray:
+    """`relight_rig_in_photograph` for face boxes of any size (`relight_lights_in_photograph_anybox`): ONE (B,Hp,Wp,3) uint8 RGB
+    composite per photograph under the rig; with one light of colour 1 it equals `relight_lights_in_photograph_anybox(...)[:, 0]`.
+    One device-to-host copy at the end."""
+    return relight_rig_in_photograph_anybox_device(model, photos_u8, boxes, mask_u8, lights, light_rgb, ambient, focal, device,
+                                                   composite_mask_u8, epoch, detail_clamp, floor, paste).cpu().numpy()
+
+
 def _rig_frames(x, out, cm, light_rgb_frames, transfer: bool, fix_border: bool) -> torch.Tensor:
     """`forward_lights`' tuple -> (B,F,H,W,3) uint8: ONE rig-frames launch on its albedo (out[0]) and final shading (out[8]), and
     the optional border fix on the (B F,H,W,3) view"""

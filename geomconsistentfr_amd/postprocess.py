@@ -13,6 +13,9 @@ Device path (HIP kernels of csrc/gcfr_postprocess.hip, no CPU fallback): `infere
                                 csrc/gcfr_fullres_box.hip
   fullres_box_composites_device the relit images carried back onto the box's pixels: the photograph relit inside the box, uint8;
                                 upsample="guided": edge-aware, csrc/gcfr_fullres_box_guided.hip
+  ingest_anybox_device          `ingest_box_device` for a box that may be SMALLER than the network's input on either axis,
+                                csrc/gcfr_fullres_anybox.hip
+  fullres_anybox_composites_device  `fullres_box_composites_device` for such a box
 
 Host side: the on-disk formats of load_data() (T8:545-556).  The numpy statements of the script lines these kernels
 implement live in oracle/postprocess_statements.py (test infrastructure, pinned to the reference's own main() by
@@ -222,10 +225,11 @@ def fullres_composites_device(photo_u8, x_lo, rendered, mask_u8, scale, detail_c
     return res
 
 
-def _check_boxes(boxes, photo_u8, h, w, what, same_size=False):
+def _check_boxes(boxes, photo_u8, h, w, what, same_size=False, any_size=False):
     """-> a contiguous (B,4) int32 numpy array of HOST boxes (x0, y0, bw, bh) that satisfy include/gcfr.h's box rules for the uint8
     photographs (B,Hp,Wp,3) and a network of (h, w), or GcfrError.  `boxes`: (4,) broadcast over the faces or (B,4); a list, a numpy
-    array or a CPU tensor of integers."""
+    array or a CPU tensor of integers.  `any_size`: the relaxed rules of the anybox entries, bw, bh >= 1 with 8 bw >= w and
+    8 bh >= h, in the place of bw >= w and bh >= h."""
     import torch
     from . import _lib
     B, Hp, Wp, _ = _check_photographs(photo_u8, 1, what, boxed=True)
@@ -247,7 +251,9 @@ def _check_boxes(boxes, photo_u8, h, w, what, same_size=False):
     for b, (x0, y0, bw, bh) in enumerate(a.tolist()):
         if x0 < 0 or y0 < 0 or x0 + bw > Wp or y0 + bh > Hp:
             raise _lib.GcfrError("%s: box %d (x0 %d, y0 %d, bw %d, bh %d) does not lie inside the %d x %d photograph" % (what, b, x0, y0, bw, bh, Wp, Hp))
-        if bw < w or bh < h:
+        if any_size and (bw < 1 or bh < 1 or 8 * bw < w or 8 * bh < h):
+            raise _lib.GcfrError("%s: box %d (%d x %d) is empty or under an eighth of the network's input (%d x %d) on an axis" % (what, b, bw, bh, w, h))
+        if not any_size and (bw < w or bh < h):
             raise _lib.GcfrError("%s: box %d (%d x %d) is smaller than the network's input (%d x %d)" % (what, b, bw, bh, w, h))
         if 2 * bh * h > 0x7fffffff or 2 * bw * w > 0x7fffffff:
             raise _lib.GcfrError("%s: box %d: 2 bh h and 2 bw w must fit 31 bits" % (what, b))
@@ -324,6 +330,59 @@ def fullres_box_composites_device(photo_u8, boxes, x_lo, rendered, mask_u8, deta
     else:
         _lib.launch("gcfr_fullres_composites_box_u8", photo.device, photo, x, ren, m, m.shape[0], B, L, Hp, Wp, _host_pointer(bx), h, w,
                     int(bool(paste)), float(floor), float(detail_clamp), res, _lib.STREAM)
+    return res
+
+
+def ingest_anybox_device(photo_u8, boxes, size):
+    """`ingest_box_device` for a face box that may be SMALLER than the network's input, on either axis or on both: bw, bh >= 1 with
+    8 bw >= w and 8 bh >= h -> (B,h,w,3) f32 in [0,1].  Each axis on its own: an axis at least as long as the network's is
+    `ingest_box_device`'s exact area mean; a shorter one is magnified by the half-pixel-centre bilinear rule written in integers
+    (two taps of weights 2n - rem and rem over 2n).  One exact 64-bit integer, one f64 division, one rounding to f32 for all four
+    combinations (include/gcfr.h states it; csrc/gcfr_fullres_anybox.hip); with bw >= w and bh >= h, `ingest_box_device`'s bits
+    from this entry's own kernel.  One launch per 32 faces, no host synchronisation; a malformed input raises GcfrError before
+    anything is loaded or launched."""
+    import torch
+    from . import _lib
+    what = "ingest_anybox_device"
+    h, w = (size, size) if isinstance(size, int) else (tuple(size) if isinstance(size, (tuple, list)) and len(size) == 2 else (None, None))
+    bx = _check_boxes(boxes, photo_u8, h, w, what, any_size=True)
+    _lib.require_device(photo_u8)
+    photo = photo_u8.detach().contiguous()
+    B, Hp, Wp, _ = photo.shape
+    x_lo = torch.empty((B, h, w, 3), dtype=torch.float32, device=photo.device)
+    _lib.launch("gcfr_ingest_anybox_u8", photo.device, photo, B, Hp, Wp, _host_pointer(bx), h, w, x_lo, _lib.STREAM)
+    return x_lo
+
+
+def fullres_anybox_composites_device(photo_u8, boxes, x_lo, rendered, mask_u8, detail_clamp=4.0, floor=1.0, paste=True, out=None):
+    """`fullres_box_composites_device` for a face box that may be SMALLER than the network's input on either axis (the box rules of
+    `ingest_anybox_device`); operands, `paste` and `out` as there.  The relit image, x_lo and the mask are carried to the box per
+    axis: an axis at least as long as the network's by that entry's two taps and one lerp, a shorter one by the exact-footprint
+    area mean of the at most nine network pixels a box pixel covers (f64 sum of integer weight times value, one division by n, one
+    rounding; include/gcfr.h states every operation; csrc/gcfr_fullres_anybox.hip).  Horizontal first, then vertical.  With
+    bw >= w and bh >= h these are `fullres_box_composites_device`'s bytes, from this entry's own kernel: there is no dispatch
+    between the two.  There is no guided upsample here.  ONE launch per 32 faces for all L lights; large, small and mixed boxes
+    may share a launch.  NOT DIFFERENTIABLE.  No host synchronisation; a malformed input raises GcfrError before anything is
+    loaded or launched."""
+    import torch
+    from . import _lib
+    what = "fullres_anybox_composites_device"
+    if not isinstance(paste, (bool, int)) or paste not in (0, 1):
+        raise _lib.GcfrError("%s: paste must be True or False; got %r" % (what, paste))
+    _check_composite_tensors(what, x_lo, rendered, mask_u8, out)
+    if x_lo.dim() != 4 or x_lo.shape[-1] != 3 or min(x_lo.shape) < 1:
+        raise _lib.GcfrError("%s: x_lo must be (B,h,w,3); got %s" % (what, tuple(x_lo.shape)))
+    h, w = int(x_lo.shape[1]), int(x_lo.shape[2])
+    bx = _check_boxes(boxes, photo_u8, h, w, what, same_size=not paste, any_size=True)
+    B, Hp, Wp, _ = photo_u8.shape
+    window = (Hp, Wp) if paste else (int(bx[0, 3]), int(bx[0, 2]))
+    photo, x, ren, m, L, shape = _composite_operands(what, photo_u8, x_lo, rendered, mask_u8, out, detail_clamp, floor, B, h, w, window,
+                                                     frame=", in the box's frame")
+    if out is not None and out.data_ptr() < photo.data_ptr() + photo.numel() and photo.data_ptr() < out.data_ptr() + out.numel():
+        raise _lib.GcfrError("%s: out must not overlap the photographs" % what)
+    res = torch.empty(shape, dtype=torch.uint8, device=photo.device) if out is None else out
+    _lib.launch("gcfr_fullres_composites_anybox_u8", photo.device, photo, x, ren, m, m.shape[0], B, L, Hp, Wp, _host_pointer(bx), h, w,
+                int(bool(paste)), float(floor), float(detail_clamp), res, _lib.STREAM)
     return res
 
 

@@ -770,6 +770,44 @@ int gcfr_fullres_composites_box_guided_u8(const uint8_t *photo_u8, const float *
                                           int32_t h, int32_t w, int32_t paste, float floor, float detail_clamp, float range_sigma,
                                           uint8_t *out_u8, void *stream);
 
+/*
+ * The box entries WITHOUT the rule bw >= w, bh >= h (csrc/gcfr_fullres_anybox.hip): a face smaller than the network's input on
+ * either axis, or on both.  Operands, layouts, the host `boxes`, `paste` and the parameter lists are exactly gcfr_ingest_box_u8's
+ * and gcfr_fullres_composites_box_u8's; the two entries above keep refusing small boxes.  Each axis is treated on its own; below,
+ * an axis has the box's length nb (bh or bw) and the network's length n (h or w).
+ * Box rules, each GCFR_ERR_INVALID_ARGUMENT before any launch: 0 <= x0, x0 + bw <= Wp, 0 <= y0, y0 + bh <= Hp; nb >= 1 and
+ * 8 nb >= n on both axes (the cap bounds every loop below at nine taps per axis); 2 bh h and 2 bw w fit 31 bits; Hp Wp < 2^31 and
+ * B ceil(Hp Wp / 1024) < 2^31; with paste = 0 all boxes share one size.
+ *   Ingest, one exact integer and one rounding for all four axis combinations:
+ *            x_lo[i,j,c] = (float)((double)S / (255.0 Dy Dx)), S = sum_y sum_x wy wx byte in 64 bits.
+ *            Axis with nb >= n (gcfr_ingest_box_u8's area mean): wy(i,y) = max(0, min((y+1) n, (i+1) nb) - max(y n, i nb)), D = nb.
+ *            Axis with nb < n (magnify; half-pixel-centre bilinear in integers): N = max((2i+1) nb - n, 0), i0 = N div 2n,
+ *            rem = N - i0 2n, i1 = min(i0 + 1, nb - 1); tap i0 weighs 2n - rem and tap i1 weighs rem (where i1 = i0 the pixel
+ *            receives both weights), D = 2n.  255 Dy Dx is exact in f64.
+ *   Carry to the box: the operator that the box entries call Up, applied to x_lo, to the mask quotient (float)mask_u8 / 255.0f
+ *            and to every plane of `rendered`.  Separable: horizontal first on every tap row, each result rounded to f32, then
+ *            vertical.
+ *            Axis with nb >= n: Up-over-the-box's two taps and t, and one lerp a0 + t (a1 - a0) in f32.
+ *            Axis with nb < n (minify; exact-footprint area mean): box index y overlaps network index i by
+ *            wt(y,i) = max(0, min((i+1) nb, (y+1) n) - max(i nb, y n)); i runs from (y n) div nb to ceil((y+1) n / nb) - 1, at
+ *            most nine taps, whose weights sum to n.  The value is (float)(acc / (double)n), acc the f64 sum, starting from +0.0,
+ *            of (double)wt (double)v in ascending i.  wt <= nb < 2^15, so every product is exact; every f64 addition is separate.
+ *   Composite: inside the box the p, xl, d, m, r, v and the byte of gcfr_fullres_composites_u8 through the same device functions,
+ *            with the carrying operator in the place of Up.  A pixel of the output window outside the box is the photograph's
+ *            byte, for every light.  mask_u8 stays at the network's resolution, in the box's frame.
+ *   Anchor, with no tolerance: with bw >= w and bh >= h every formula is the box entries' own and the bits and bytes are theirs.
+ * Refusals: gcfr_ingest_box_u8's and gcfr_fullres_composites_box_u8's with the box rules above.  32 faces per launch with the boxes
+ * by value; allocates nothing, never synchronises, may be captured into a graph.  Bit-equal to the numpy restatement
+ * (tests/fullres_anybox_emulation.py).  Three dwords per four pixels on gcfr_fullres_composites_box_u8's conditions, the copy outside
+ * the box included; one element at a time otherwise (same results).
+ */
+int gcfr_ingest_anybox_u8(const uint8_t *photo_u8, int32_t B, int32_t Hp, int32_t Wp, const int32_t *boxes, int32_t h, int32_t w,
+                          float *x_lo_out, void *stream);
+int gcfr_fullres_composites_anybox_u8(const uint8_t *photo_u8, const float *x_lo, const float *rendered, const uint8_t *mask_u8,
+                                      int32_t mask_batch, int32_t B, int32_t L, int32_t Hp, int32_t Wp, const int32_t *boxes,
+                                      int32_t h, int32_t w, int32_t paste, float floor, float detail_clamp, uint8_t *out_u8,
+                                      void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Environment-map lighting: a lat-long radiance map integrated into the `rgb` (colour x weight per light) of the light-rig stage
  * above (csrc/gcfr_environment.hip).  Every texel belongs to the light direction nearest to it; a light's rgb is the
