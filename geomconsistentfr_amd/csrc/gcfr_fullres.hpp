@@ -17,6 +17,8 @@
 // their kernels.
 // gcfr_fullres_anybox.hip (a box smaller than the network's input on either axis) is a fifth user: the same arithmetic, vector-path
 // pieces, composite_pixel (over its own carrier, AnyCarrier) and per-face pieces, and the relaxed box rules anyboxes_ok below.
+// gcfr_fullres_group.hip (every face of a photograph in one launch) is a sixth: that carrier (gcfr_fullres_anybox.hpp) over the
+// same arithmetic, with the running bytes in the place of the photograph's.
 #pragma once
 
 #include <type_traits>

@@ -415,6 +415,65 @@ def relight_rig_in_photograph_anybox(model, photos_u8, boxes, mask_u8, lights, l
                                                    composite_mask_u8, epoch, detail_clamp, floor, paste).cpu().numpy()
 
 
+def _check_host_photo_index(photo_index):
+    if torch.is_tensor(photo_index) and photo_index.is_cuda:
+        raise GcfrError("photo_index are HOST integers, one photograph per face; got a tensor on %s" % photo_index.device)
+
+
+@torch.no_grad()
+def relight_lights_in_group_photograph_device(model, photos_u8, boxes, photo_index, mask_u8, lights, ambient: float = 0.5,
+                                              focal: float = None, device="cuda", composite_mask_u8=None, epoch: int = 200,
+                                              detail_clamp: float = 4.0, floor: float = 1.0) -> torch.Tensor:
+    """`relight_lights_in_group_photograph` up to the bytes ON THE DEVICE: (P,L,Hp,Wp,3) uint8 tensor, nothing copied back.
+    `photos_u8` / `mask_u8` / `lights` may already be device tensors; `boxes` and `photo_index` stay on the host."""
+    _check_host_boxes(boxes)
+    _check_host_photo_index(photo_index)
+    return _relight_photographs(model, photos_u8, mask_u8, lights, ambient, focal, device, composite_mask_u8, epoch,
+                                lambda ph: pp.ingest_group_device(ph, boxes, photo_index, _network_size(mask_u8)),
+                                lambda ph, *a: pp.fullres_group_composites_device(ph, boxes, photo_index, *a, detail_clamp, floor))
+
+
+@torch.no_grad()
+def relight_lights_in_group_photograph(model, photos_u8, boxes, photo_index, mask_u8, lights, ambient: float = 0.5, focal: float = None,
+                                       device="cuda", composite_mask_u8=None, epoch: int = 200, detail_clamp: float = 4.0,
+                                       floor: float = 1.0) -> np.ndarray:
+    """EVERY face of a GROUP PHOTOGRAPH relit: photos_u8 (P,Hp,Wp,3) uint8 (or one (Hp,Wp,3)), B faces with host `boxes` (B,4) of
+    any size (`relight_lights_in_photograph_anybox`'s rules) and host `photo_index` (B,) naming each face's photograph (any order; a
+    photograph may have no face, one or many; None: all faces in the one photograph) -> (P,L,Hp,Wp,3) uint8 RGB: every photograph
+    under every one of `lights` (L,3) with ALL of its faces relit.  Three steps on the device:
+    `postprocess.ingest_group_device` (the photographs are not copied per face), ONE `forward_lights` pass on all B faces, then
+    `postprocess.fullres_group_composites_device`: one pass over each photograph's bytes, per photograph the chain of
+    `relight_lights_in_photograph_anybox`'s composite over its faces in ascending face index (see there for overlapping faces).
+    `mask_u8` / `composite_mask_u8` are in the boxes' frame and shared by the faces.  Everything else is
+    `relight_lights_in_photograph_anybox`'s; there is no `paste=False`.  One device-to-host copy of the result at the end."""
+    return relight_lights_in_group_photograph_device(model, photos_u8, boxes, photo_index, mask_u8, lights, ambient, focal, device,
+                                                     composite_mask_u8, epoch, detail_clamp, floor).cpu().numpy()
+
+
+@torch.no_grad()
+def relight_rig_in_group_photograph_device(model, photos_u8, boxes, photo_index, mask_u8, lights, light_rgb, ambient: float = 0.5,
+                                           focal: float = None, device="cuda", composite_mask_u8=None, epoch: int = 200,
+                                           detail_clamp: float = 4.0, floor: float = 1.0) -> torch.Tensor:
+    """`relight_rig_in_group_photograph` up to the bytes ON THE DEVICE: (P,Hp,Wp,3) uint8 tensor, nothing copied back."""
+    _check_host_boxes(boxes)
+    _check_host_photo_index(photo_index)
+    return _relight_photographs(model, photos_u8, mask_u8, lights, ambient, focal, device, composite_mask_u8, epoch,
+                                lambda ph: pp.ingest_group_device(ph, boxes, photo_index, _network_size(mask_u8)),
+                                lambda ph, *a: pp.fullres_group_composites_device(ph, boxes, photo_index, *a, detail_clamp, floor),
+                                light_rgb, rig=True)
+
+
+@torch.no_grad()
+def relight_rig_in_group_photograph(model, photos_u8, boxes, photo_index, mask_u8, lights, light_rgb, ambient: float = 0.5,
+                                    focal: float = None, device="cuda", composite_mask_u8=None, epoch: int = 200,
+                                    detail_clamp: float = 4.0, floor: float = 1.0) -> np.ndarray:
+    """`relight_rig` on every face of a group photograph (`relight_lights_in_group_photograph`): ONE (P,Hp,Wp,3) uint8 RGB composite
+    per photograph under the rig of `lights` with colour x weight `light_rgb`, all of its faces relit; with one light of colour 1 it
+    equals `relight_lights_in_group_photograph(...)[:, 0]`.  One device-to-host copy at the end."""
+    return relight_rig_in_group_photograph_device(model, photos_u8, boxes, photo_index, mask_u8, lights, light_rgb, ambient, focal, device,
+                                                  composite_mask_u8, epoch, detail_clamp, floor).cpu().numpy()
+
+
 def _rig_frames(x, out, cm, light_rgb_frames, transfer: bool, fix_border: bool) -> torch.Tensor:
     """`forward_lights`' tuple -> (B,F,H,W,3) uint8: ONE rig-frames launch on its albedo (out[0]) and final shading (out[8]), and
     the optional border fix on the (B F,H,W,3) view"""

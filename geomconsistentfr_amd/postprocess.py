@@ -16,6 +16,9 @@ Device path (HIP kernels of csrc/gcfr_postprocess.hip, no CPU fallback): `infere
   ingest_anybox_device          `ingest_box_device` for a box that may be SMALLER than the network's input on either axis,
                                 csrc/gcfr_fullres_anybox.hip
   fullres_anybox_composites_device  `fullres_box_composites_device` for such a box
+  ingest_group_device           `ingest_anybox_device` for B faces spread over P photographs (a group photograph),
+                                csrc/gcfr_fullres_group.hip
+  fullres_group_composites_device   every face of a photograph relit in ONE pass over it: one photograph per photograph out
 
 Host side: the on-disk formats of load_data() (T8:545-556).  The numpy statements of the script lines these kernels
 implement live in oracle/postprocess_statements.py (test infrastructure, pinned to the reference's own main() by
@@ -140,14 +143,16 @@ def _check_composite_tensors(what, x_lo, rendered, mask_u8, out):
                        rendered=_lib.FLOATS, mask_u8=torch.uint8, out=torch.uint8)
 
 
-def _composite_operands(what, photo_u8, x_lo, rendered, mask_u8, out, detail_clamp, floor, B, h, w, window, frame=""):
+def _composite_operands(what, photo_u8, x_lo, rendered, mask_u8, out, detail_clamp, floor, B, h, w, window, frame="", images=None):
     """The operands both composites share, for B faces of a network of (h, w) and an output `window` (rows, columns), or GcfrError
-    -> the photographs, x_lo, rendered and the mask as the kernels read them, L, and the result's shape."""
+    -> the photographs, x_lo, rendered and the mask as the kernels read them, L, and the result's shape.  `images`: the number of
+    images that come back where it is not one per face (the group entry's P)."""
     import torch
     from . import _lib
     _lib.check_shape("x_lo", x_lo, (B, h, w, 3))
     L = rendered.shape[1] if rendered.dim() == 5 else 1
-    shape = ((B, L) if rendered.dim() == 5 else (B,)) + tuple(window) + (3,)
+    n = B if images is None else images
+    shape = ((n, L) if rendered.dim() == 5 else (n,)) + tuple(window) + (3,)
     _lib.check_shape("rendered", rendered, (B, 3, h, w), (B, L, 3, h, w))
     if not 1 <= L <= FULLRES_MAX_LIGHTS:
         raise _lib.GcfrError("%s: rendered %s: 1 <= L <= %d" % (what, tuple(rendered.shape), FULLRES_MAX_LIGHTS))
@@ -225,14 +230,17 @@ def fullres_composites_device(photo_u8, x_lo, rendered, mask_u8, scale, detail_c
     return res
 
 
-def _check_boxes(boxes, photo_u8, h, w, what, same_size=False, any_size=False):
+def _check_boxes(boxes, photo_u8, h, w, what, same_size=False, any_size=False, faces=None):
     """-> a contiguous (B,4) int32 numpy array of HOST boxes (x0, y0, bw, bh) that satisfy include/gcfr.h's box rules for the uint8
     photographs (B,Hp,Wp,3) and a network of (h, w), or GcfrError.  `boxes`: (4,) broadcast over the faces or (B,4); a list, a numpy
     array or a CPU tensor of integers.  `any_size`: the relaxed rules of the anybox entries, bw, bh >= 1 with 8 bw >= w and
-    8 bh >= h, in the place of bw >= w and bh >= h."""
+    8 bh >= h, in the place of bw >= w and bh >= h.  `faces`: B faces over the P photographs (P,Hp,Wp,3) of the group entries, in
+    the place of one face per photograph."""
     import torch
     from . import _lib
     B, Hp, Wp, _ = _check_photographs(photo_u8, 1, what, boxed=True)
+    if faces is not None:
+        B = faces
     if any(isinstance(n, bool) or not isinstance(n, int) or n < 1 for n in (h, w)):
         raise _lib.GcfrError("%s: the network's size (h, w) must be positive integers; got %r" % (what, (h, w)))
     if torch.is_tensor(boxes):
@@ -383,6 +391,99 @@ def fullres_anybox_composites_device(photo_u8, boxes, x_lo, rendered, mask_u8, d
     res = torch.empty(shape, dtype=torch.uint8, device=photo.device) if out is None else out
     _lib.launch("gcfr_fullres_composites_anybox_u8", photo.device, photo, x, ren, m, m.shape[0], B, L, Hp, Wp, _host_pointer(bx), h, w,
                 int(bool(paste)), float(floor), float(detail_clamp), res, _lib.STREAM)
+    return res
+
+
+def _check_photo_index(photo_index, photo_u8, what, faces=None, boxes=None):
+    """-> a contiguous (B,) int32 numpy array of HOST indices: the photograph of each of the B faces of the group entries, every one in
+    [0, P) for the uint8 photographs (P,Hp,Wp,3), or GcfrError.  `photo_index`: a list, a numpy array or a CPU tensor of integers
+    (B,); None: all zeros, which needs P == 1.  B is `faces` where the caller knows it (x_lo's), else photo_index's length, else the
+    number of rows of `boxes`."""
+    import torch
+    from . import _lib
+    P = _check_photographs(photo_u8, 1, what, boxed=True)[0]
+    if photo_index is None:
+        if P != 1:
+            raise _lib.GcfrError("%s: photo_index=None means one photograph for every face; got %d photographs" % (what, P))
+        if faces is None:
+            shape = tuple(boxes.shape) if torch.is_tensor(boxes) else np.shape(boxes) if isinstance(boxes, (list, tuple, np.ndarray)) else ()
+            faces = int(shape[0]) if len(shape) == 2 else 1
+        return np.zeros((faces,), np.int32)
+    if torch.is_tensor(photo_index):
+        if photo_index.is_cuda:
+            raise _lib.GcfrError("%s: photo_index are HOST integers (the entry bakes them into its launches); got a tensor on %s"
+                                 % (what, photo_index.device))
+        photo_index = photo_index.detach().numpy()
+    try:
+        a = np.asarray(photo_index)
+    except Exception as e:
+        raise _lib.GcfrError("%s: photo_index must be integers (B,): %s" % (what, e))
+    if a.dtype.kind not in "iu":
+        raise _lib.GcfrError("%s: photo_index must be integers, got %s" % (what, a.dtype))
+    if a.ndim != 1 or a.shape[0] < 1 or (faces is not None and a.shape[0] != faces):
+        raise _lib.GcfrError("%s: photo_index must be (%s,), one photograph per face; got %s" % (what, "B" if faces is None else faces, a.shape))
+    a = a.astype(np.int64)
+    if a.min() < 0 or a.max() >= P:
+        raise _lib.GcfrError("%s: photo_index must lie in [0, %d) for %d photographs; got %d .. %d" % (what, P, P, a.min(), a.max()))
+    return np.ascontiguousarray(a, dtype=np.int32)
+
+
+def ingest_group_device(photo_u8, boxes, photo_index, size):
+    """`ingest_anybox_device` for a GROUP PHOTOGRAPH: photo_u8 (P,Hp,Wp,3) uint8, B faces with host `boxes` (B,4) (or (4,) for every
+    face) under that entry's rules and host `photo_index` (B,) naming each face's photograph -- a list, a numpy array or a CPU
+    tensor of integers in [0, P), in any order; a photograph may have no face, one or many; None: every face in the one photograph
+    (P == 1) -> (B,h,w,3) f32 in [0,1].  The bits are `ingest_anybox_device(photo_u8[photo_index], boxes, size)`'s, and the
+    photographs are neither gathered nor copied (include/gcfr.h states it; csrc/gcfr_fullres_group.hip).  One launch per 32 faces,
+    no host synchronisation; a malformed input raises GcfrError before anything is loaded or launched."""
+    import torch
+    from . import _lib
+    what = "ingest_group_device"
+    h, w = (size, size) if isinstance(size, int) else (tuple(size) if isinstance(size, (tuple, list)) and len(size) == 2 else (None, None))
+    pi = _check_photo_index(photo_index, photo_u8, what, boxes=boxes)
+    B = int(pi.shape[0])
+    bx = _check_boxes(boxes, photo_u8, h, w, what, any_size=True, faces=B)
+    _lib.require_device(photo_u8)
+    photo = photo_u8.detach().contiguous()
+    P, Hp, Wp, _ = photo.shape
+    x_lo = torch.empty((B, h, w, 3), dtype=torch.float32, device=photo.device)
+    _lib.launch("gcfr_ingest_group_u8", photo.device, photo, P, Hp, Wp, _host_pointer(bx), _host_pointer(pi), B, h, w, x_lo, _lib.STREAM)
+    return x_lo
+
+
+def fullres_group_composites_device(photo_u8, boxes, photo_index, x_lo, rendered, mask_u8, detail_clamp=4.0, floor=1.0, out=None):
+    """EVERY face of a photograph relit in one pass over the photograph: photo_u8 (P,Hp,Wp,3) uint8; `boxes` and `photo_index` as in
+    `ingest_group_device`; x_lo (B,h,w,3) f32, the network's input (`ingest_group_device`); rendered (B,L,3,h,w) -> (P,L,Hp,Wp,3), or
+    (B,3,h,w) -> (P,Hp,Wp,3); mask_u8 (1|B,h,w) or (h,w) uint8, per FACE and in the box's frame, exactly as
+    `fullres_anybox_composites_device` takes them.  Per photograph and light the result is the CHAIN of that entry's pasted
+    composite over the photograph's faces in ascending face index, byte for byte: the running image starts as the photograph; a
+    face relights it inside its box where its carried mask is positive, reading the running bytes where that entry reads the
+    photograph's, and every step rounds to a byte (include/gcfr.h states it; csrc/gcfr_fullres_group.hip).  Where at most one face
+    relights a pixel the byte is that entry's; where two carried masks are positive the second face's gain multiplies the first's
+    result, so order matters there and nowhere else.  A photograph without faces comes back as it is for every light; all faces of a
+    photograph share the light index.  With `photo_index = arange(B)` and P = B these are `fullres_anybox_composites_device`'s
+    bytes.  ONE launch per 32 faces, whole photographs per launch; a photograph with more than 32 faces is continued by further
+    launches on the same stream.  There is no `paste=False`, no guided upsample.  `out`: a contiguous uint8 buffer of the result's
+    shape that is written and returned; it must not overlap the photographs.  NOT DIFFERENTIABLE.  No host synchronisation; a
+    malformed input raises GcfrError before anything is loaded or launched."""
+    import torch
+    from . import _lib
+    what = "fullres_group_composites_device"
+    _check_composite_tensors(what, x_lo, rendered, mask_u8, out)
+    if x_lo.dim() != 4 or x_lo.shape[-1] != 3 or min(x_lo.shape) < 1:
+        raise _lib.GcfrError("%s: x_lo must be (B,h,w,3); got %s" % (what, tuple(x_lo.shape)))
+    B, h, w = int(x_lo.shape[0]), int(x_lo.shape[1]), int(x_lo.shape[2])
+    pi = _check_photo_index(photo_index, photo_u8, what, faces=B)
+    bx = _check_boxes(boxes, photo_u8, h, w, what, any_size=True, faces=B)
+    P, Hp, Wp, _ = photo_u8.shape
+    # (a photograph that is not contiguous is copied below and cannot overlap anything; where the tensors live is the last check)
+    if (out is not None and photo_u8.is_contiguous() and out.data_ptr() < photo_u8.data_ptr() + photo_u8.numel()
+            and photo_u8.data_ptr() < out.data_ptr() + out.numel()):
+        raise _lib.GcfrError("%s: out must not overlap the photographs" % what)
+    photo, x, ren, m, L, shape = _composite_operands(what, photo_u8, x_lo, rendered, mask_u8, out, detail_clamp, floor, B, h, w, (Hp, Wp),
+                                                     frame=", in the box's frame", images=P)
+    res = torch.empty(shape, dtype=torch.uint8, device=photo.device) if out is None else out
+    _lib.launch("gcfr_fullres_composites_group_u8", photo.device, photo, x, ren, m, m.shape[0], P, B, L, Hp, Wp, _host_pointer(bx),
+                _host_pointer(pi), h, w, float(floor), float(detail_clamp), res, _lib.STREAM)
     return res
 
 

@@ -808,6 +808,54 @@ int gcfr_fullres_composites_anybox_u8(const uint8_t *photo_u8, const float *x_lo
                                       int32_t h, int32_t w, int32_t paste, float floor, float detail_clamp, uint8_t *out_u8,
                                       void *stream);
 
+/*
+ * GROUP PHOTOGRAPHS (csrc/gcfr_fullres_group.hip): every face of a photograph relit in one pass over the photograph's bytes.  The
+ * any-size entries above take one box per photograph and return one photograph per face; here B >= 1 faces are spread over P
+ * photographs and ONE photograph per photograph comes back.
+ *   photo_u8     (P,Hp,Wp,3) u8
+ *   boxes        (B,4) i32 HOST (x0, y0, bw, bh) under gcfr_ingest_anybox_u8's box rules (inside the photograph, bw, bh >= 1,
+ *                8 bw >= w, 8 bh >= h, 2 bh h and 2 bw w in 31 bits)
+ *   photo_index  (B,) i32 HOST, 0 <= photo_index[b] < P: the photograph of face b.  Any order; a photograph may have no face, one
+ *                face or many, more than 32 included.  Read during the call like `boxes`, and handed to the kernels by value.
+ *   x_lo         (B,h,w,3) f32;  rendered (B,L,3,h,w) f32;  mask_u8 (mask_batch,h,w) u8, mask_batch in {1, B}: per FACE, in the
+ *                box's frame, exactly as gcfr_fullres_composites_anybox_u8 takes them
+ *   out_u8       (P,L,Hp,Wp,3) u8 out
+ * Ingest: x_lo_out[b] is gcfr_ingest_anybox_u8's ingest of box b of photograph photo_index[b] -- the bits that entry returns for
+ * the gathered photographs photo_u8[photo_index] -- and the photographs are neither gathered nor copied.
+ * Composite: for every photograph q and every light l the result is the CHAIN of gcfr_fullres_composites_anybox_u8's pasted
+ * composite over the faces of q (photo_index[b] = q) in ascending face index b.  The running image starts as the photograph.  Face b
+ * applies that entry's composite (the carrying operator, p, xl, d, m, r, v and the byte, through the same device functions) inside
+ * its box, with the RUNNING bytes wherever that entry reads the photograph's: p in the blend v = p + m (r d - p) and p in the
+ * quotient d.  x_lo, rendered and the mask are face b's own.  Where face b's carried mask m is 0, and outside its box, the running
+ * byte is kept.  Every step rounds to a byte, as a call of that entry does.
+ *   Consequences.  Where at most one face relights a pixel (m > 0 inside its box), the byte is
+ *            gcfr_fullres_composites_anybox_u8's.  Where two carried masks are positive, the second face's relighting gain
+ *            multiplies the first face's result, up to the clamps and the intermediate byte: order matters there and nowhere else.
+ *            A photograph without faces is returned as it is, for every light.  All faces of a photograph share the light index l.
+ *   Anchor, with no tolerance anywhere, overlaps included: the result equals gcfr_fullres_composites_anybox_u8 (paste = 1) called
+ *            once per face with the L lights as its batch -- photo_u8 the running (L,Hp,Wp,3), the box and x_lo[b] repeated L
+ *            times, rendered[b] passed as (L,1,3,h,w) -- and its output taken as the next running image.  With
+ *            photo_index[b] = b and P = B the bytes are those of ONE call of that entry.
+ * Refusals, each GCFR_ERR_INVALID_ARGUMENT before any launch: a NULL pointer (`boxes` and `photo_index` included); B < 1, P < 1; the
+ * box rules; a photo_index outside [0, P); everything gcfr_fullres_composites_u8 refuses of L, mask_batch, detail_clamp and floor;
+ * Hp Wp >= 2^31 or P ceil(Hp Wp / 1024) >= 2^31; an out_u8 whose bytes overlap photo_u8's (the ingest: x_lo_out == photo_u8).
+ * There is no paste = 0, no guided carrying and no gradient.
+ * Launches: a workgroup owns 1024 consecutive pixels of ONE photograph and walks that photograph's faces in order; a launch covers
+ * whole photographs with at most 32 face slots in all (boxes, face indices and each photograph's slot range by value: nothing is
+ * uploaded, no device scratch, capture-safe).  The running bytes live in out_u8: the first face that relights a pixel starts from
+ * the photograph's bytes, a later one reads back what the same thread stored for that light.  A photograph with more than 32 faces
+ * gets continuation launches on the same stream, which start from out_u8 and write only what their faces relight.  A pixel no face
+ * relights is copied once per light.  Three dwords per four pixels when Wp is a multiple of 4 and out_u8 is 4-byte aligned; one
+ * element at a time otherwise (same results).  Allocates nothing on the device, never synchronises.  Bit-equal to the numpy
+ * restatement (tests/fullres_group_emulation.py).
+ */
+int gcfr_ingest_group_u8(const uint8_t *photo_u8, int32_t P, int32_t Hp, int32_t Wp, const int32_t *boxes, const int32_t *photo_index,
+                         int32_t B, int32_t h, int32_t w, float *x_lo_out, void *stream);
+int gcfr_fullres_composites_group_u8(const uint8_t *photo_u8, const float *x_lo, const float *rendered, const uint8_t *mask_u8,
+                                     int32_t mask_batch, int32_t P, int32_t B, int32_t L, int32_t Hp, int32_t Wp, const int32_t *boxes,
+                                     const int32_t *photo_index, int32_t h, int32_t w, float floor, float detail_clamp,
+                                     uint8_t *out_u8, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Environment-map lighting: a lat-long radiance map integrated into the `rgb` (colour x weight per light) of the light-rig stage
  * above (csrc/gcfr_environment.hip).  Every texel belongs to the light direction nearest to it; a light's rgb is the
