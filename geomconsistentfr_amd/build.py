@@ -24,7 +24,8 @@ LIB_PATH = os.path.join(LIB_DIR, "libgcfr_hip.so")
 SOURCES = ["gcfr_shadow.hip", "gcfr_shade.hip", "gcfr_backward.hip", "gcfr_normals.hip", "gcfr_postprocess.hip",
            "gcfr_dataset.hip", "gcfr_losses.hip", "gcfr_supervised_losses.hip", "gcfr_light_rig.hip", "gcfr_environment.hip",
            "gcfr_light_fit.hip", "gcfr_rig_frames.hip", "gcfr_fullres.hip", "gcfr_fullres_guided.hip",
-           "gcfr_fullres_box.hip", "gcfr_fullres_box_guided.hip", "gcfr_fullres_anybox.hip", "gcfr_fullres_group.hip"]
+           "gcfr_fullres_box.hip", "gcfr_fullres_box_guided.hip", "gcfr_fullres_anybox.hip", "gcfr_fullres_group.hip",
+           "gcfr_fullres_affine.hip"]
 MARCH_UNIT = "gcfr_march_unit.hip"
 # (tile width, samples per group): the default shape first
 MARCH_UNITS = [(16, 4), (16, 2), (16, 1), (8, 4), (8, 2), (8, 1), (32, 4), (32, 2), (32, 1), (64, 4), (64, 2), (64, 1)]

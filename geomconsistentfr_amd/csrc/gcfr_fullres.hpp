@@ -19,6 +19,9 @@
 // pieces, composite_pixel (over its own carrier, AnyCarrier) and per-face pieces, and the relaxed box rules anyboxes_ok below.
 // gcfr_fullres_group.hip (every face of a photograph in one launch) is a sixth: that carrier (gcfr_fullres_anybox.hpp) over the
 // same arithmetic, with the running bytes in the place of the photograph's.
+// gcfr_fullres_affine.hip (a rotated face under a 2 x 3 affine map) is a seventh: the same arithmetic, vector-path pieces,
+// composite_pixel (over its own carrier, AffineCarrier), per-face pieces, box_shape and fullres_operands; its maps travel in a
+// block of its own (AffineArgs) with kBoxFaces faces per launch.
 #pragma once
 
 #include <type_traits>

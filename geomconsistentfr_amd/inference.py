@@ -415,6 +415,99 @@ def relight_rig_in_photograph_anybox(model, photos_u8, boxes, mask_u8, lights, l
                                                    composite_mask_u8, epoch, detail_clamp, floor, paste).cpu().numpy()
 
 
+LIGHT_FRAMES = ("face", "photograph")
+
+
+def lights_in_face_frame(lights, photo_to_net, faces: int):
+    """Light directions given in the PHOTOGRAPH'S frame (+x right, +y up, as everywhere) turned into each face's own frame by the
+    rotation part of that face's map photograph -> network: `lights` (L,3) | (B,L,3) (an array or a tensor, on any device) and
+    `photo_to_net` (2,3) | (B,2,3) host numbers (the I of `postprocess.quantise_affine`, integers or not: only ratios are read) ->
+    (B,L,3) f32 where `lights` live.  The angle of face b is phi = atan2(I10 - I01, I00 + I11); in the lights' frame, whose y axis
+    points up while the image's points down, x' = cos(phi) x + sin(phi) y and y' = -sin(phi) x + cos(phi) y; z is untouched."""
+    I = np.asarray(photo_to_net.detach().numpy() if torch.is_tensor(photo_to_net) else photo_to_net, dtype=np.float64)
+    if I.shape not in ((2, 3), (faces, 2, 3)):
+        raise GcfrError("photo_to_net must be (2,3) or (%d,2,3); got %s" % (faces, I.shape))
+    I = np.broadcast_to(I, (faces, 2, 3))
+    up, along = I[:, 1, 0] - I[:, 0, 1], I[:, 0, 0] + I[:, 1, 1]                   # (sin phi, cos phi) times twice the scale
+    length = np.hypot(up, along)
+    if not np.isfinite(length).all() or (length == 0).any():
+        raise GcfrError("photo_to_net has no rotation part to read an angle from (a mirror image, or not finite)")
+    t = _as(lights, None, torch.float64, single=1)
+    if t.dim() not in (2, 3) or t.shape[-1] != 3 or (t.dim() == 3 and t.shape[0] != faces):
+        raise GcfrError("lights must be (L,3) or (%d,L,3); got %s" % (faces, tuple(t.shape)))
+    t = t[None].expand(faces, -1, -1) if t.dim() == 2 else t
+    # cos phi and sin phi as quotients (exact at whole quarter turns); the two products and the sum in f64, rounded once to f32
+    co, si = (torch.from_numpy(v / length).to(t.device)[:, None] for v in (along, up))
+    x, y = t[..., 0], t[..., 1]
+    return torch.stack([co * x + si * y, co * y - si * x, t[..., 2]], -1).to(torch.float32).contiguous()
+
+
+def _affine_entry(photos_u8, net_to_photo, lights, light_frame, device):
+    """what the four affine entries do before the pass: the photographs on the device, the host map as `quantise_affine`'s integer
+    pair (so that the ingest, the composite and the lights read the same integers), and the lights in the faces' frame"""
+    if light_frame not in LIGHT_FRAMES:
+        raise GcfrError("light_frame must be one of %s; got %r" % (LIGHT_FRAMES, light_frame))
+    photos = _as_photographs(photos_u8, device)
+    pair = pp._affine_integers(net_to_photo, int(photos.shape[0]), "relight_in_photograph_affine")
+    if light_frame == "photograph":
+        lights = lights_in_face_frame(lights, pair[1], int(photos.shape[0]))
+    return photos, pair, lights
+
+
+@torch.no_grad()
+def relight_lights_in_photograph_affine_device(model, photos_u8, net_to_photo, mask_u8, lights, ambient: float = 0.5,
+                                               focal: float = None, device="cuda", composite_mask_u8=None, epoch: int = 200,
+                                               detail_clamp: float = 4.0, floor: float = 1.0, light_frame: str = "face") -> torch.Tensor:
+    """`relight_lights_in_photograph_affine` up to the bytes ON THE DEVICE: (B,L,Hp,Wp,3) uint8 tensor, nothing copied back.
+    `photos_u8` / `mask_u8` / `lights` may already be device tensors; `net_to_photo` stays on the host."""
+    photos, pair, lights = _affine_entry(photos_u8, net_to_photo, lights, light_frame, device)
+    return _relight_photographs(model, photos, mask_u8, lights, ambient, focal, device, composite_mask_u8, epoch,
+                                lambda ph: pp.ingest_affine_device(ph, pair, _network_size(mask_u8)),
+                                lambda ph, *a: pp.fullres_affine_composites_device(ph, pair, *a, detail_clamp, floor))
+
+
+@torch.no_grad()
+def relight_lights_in_photograph_affine(model, photos_u8, net_to_photo, mask_u8, lights, ambient: float = 0.5, focal: float = None,
+                                        device="cuda", composite_mask_u8=None, epoch: int = 200, detail_clamp: float = 4.0,
+                                        floor: float = 1.0, light_frame: str = "face") -> np.ndarray:
+    """`relight_lights_in_photograph` for a ROTATED face: `net_to_photo` is the host 2 x 3 map from the network's coordinates to the
+    photograph's -- (2,3) for every face or (B,2,3) f64, what a face aligner reports (eye line horizontal, fixed inter-ocular
+    distance) or `postprocess.affine_from_rotated_box` builds; or `postprocess.quantise_affine`'s integer pair -> (B,L,Hp,Wp,3)
+    uint8 RGB: every photograph under every one of `lights`, relit inside the tilted quad of its face and untouched outside it.
+    The same three steps with `postprocess.ingest_affine_device` (the network sees an ALIGNED face, without a host-side warp) and
+    ONE `postprocess.fullres_affine_composites_device` launch per 32 faces.  `mask_u8` / `composite_mask_u8` are in the network's
+    frame.  `light_frame`: "face" (the default) takes `lights` (L,3) | (B,L,3) in the network's frame, as everywhere else;
+    "photograph" takes them in the photograph's frame (+x right, +y up) and turns each face's copy into that face's frame by the
+    rotation part of its map (`lights_in_face_frame`; (L,3) becomes (B,L,3)), so that "light from the photograph's left" comes from
+    the photograph's left on a tilted face too.  There is always a pasted photograph: a rotated quad has no "box alone".  Everything
+    else is `relight_lights_in_photograph`'s.  One device-to-host copy of the result at the end."""
+    return relight_lights_in_photograph_affine_device(model, photos_u8, net_to_photo, mask_u8, lights, ambient, focal, device,
+                                                      composite_mask_u8, epoch, detail_clamp, floor, light_frame).cpu().numpy()
+
+
+@torch.no_grad()
+def relight_rig_in_photograph_affine_device(model, photos_u8, net_to_photo, mask_u8, lights, light_rgb, ambient: float = 0.5,
+                                            focal: float = None, device="cuda", composite_mask_u8=None, epoch: int = 200,
+                                            detail_clamp: float = 4.0, floor: float = 1.0, light_frame: str = "face") -> torch.Tensor:
+    """`relight_rig_in_photograph_affine` up to the bytes ON THE DEVICE: (B,Hp,Wp,3) uint8 tensor, nothing copied back."""
+    photos, pair, lights = _affine_entry(photos_u8, net_to_photo, lights, light_frame, device)
+    return _relight_photographs(model, photos, mask_u8, lights, ambient, focal, device, composite_mask_u8, epoch,
+                                lambda ph: pp.ingest_affine_device(ph, pair, _network_size(mask_u8)),
+                                lambda ph, *a: pp.fullres_affine_composites_device(ph, pair, *a, detail_clamp, floor),
+                                light_rgb, rig=True)
+
+
+@torch.no_grad()
+def relight_rig_in_photograph_affine(model, photos_u8, net_to_photo, mask_u8, lights, light_rgb, ambient: float = 0.5,
+                                     focal: float = None, device="cuda", composite_mask_u8=None, epoch: int = 200,
+                                     detail_clamp: float = 4.0, floor: float = 1.0, light_frame: str = "face") -> np.ndarray:
+    """`relight_rig_in_photograph` for a rotated face (`relight_lights_in_photograph_affine`, `light_frame` included): ONE
+    (B,Hp,Wp,3) uint8 RGB composite per photograph under the rig; with one light of colour 1 it equals
+    `relight_lights_in_photograph_affine(...)[:, 0]`.  One device-to-host copy at the end."""
+    return relight_rig_in_photograph_affine_device(model, photos_u8, net_to_photo, mask_u8, lights, light_rgb, ambient, focal, device,
+                                                   composite_mask_u8, epoch, detail_clamp, floor, light_frame).cpu().numpy()
+
+
 def _check_host_photo_index(photo_index):
     if torch.is_tensor(photo_index) and photo_index.is_cuda:
         raise GcfrError("photo_index are HOST integers, one photograph per face; got a tensor on %s" % photo_index.device)

@@ -19,6 +19,10 @@ Device path (HIP kernels of csrc/gcfr_postprocess.hip, no CPU fallback): `infere
   ingest_group_device           `ingest_anybox_device` for B faces spread over P photographs (a group photograph),
                                 csrc/gcfr_fullres_group.hip
   fullres_group_composites_device   every face of a photograph relit in ONE pass over it: one photograph per photograph out
+  ingest_affine_device          a ROTATED face: the photograph sampled through a 2 x 3 affine map (what a face aligner reports) ->
+                                the network's f32 input, csrc/gcfr_fullres_affine.hip
+  fullres_affine_composites_device  the relit images carried back through the inverse map onto the photograph's pixels
+  quantise_affine, affine_from_rotated_box   (host) the integer matrices those two read; the map of a rotated box
 
 Host side: the on-disk formats of load_data() (T8:545-556).  The numpy statements of the script lines these kernels
 implement live in oracle/postprocess_statements.py (test infrastructure, pinned to the reference's own main() by
@@ -484,6 +488,188 @@ def fullres_group_composites_device(photo_u8, boxes, photo_index, x_lo, rendered
     res = torch.empty(shape, dtype=torch.uint8, device=photo.device) if out is None else out
     _lib.launch("gcfr_fullres_composites_group_u8", photo.device, photo, x, ren, m, m.shape[0], P, B, L, Hp, Wp, _host_pointer(bx),
                 _host_pointer(pi), h, w, float(floor), float(detail_clamp), res, _lib.STREAM)
+    return res
+
+
+AFFINE_ONE = 1 << 14            # the fixed point of the affine entries: a matrix entry is an integer number of 2^-14 (include/gcfr.h)
+AFFINE_MAX_NORM = 8             # the longest column an affine entry takes: K(M) is 1, 2, 4 or 8
+AFFINE_MAX_SHIFT = 1 << 40      # the largest |M02|, |M12|
+
+
+def affine_sub_samples(M):
+    """K(M) of include/gcfr.h for one (2,3) integer matrix: the smallest of 1, 2, 4, 8 with K^2 ONE^2 >= the longer column's
+    squared length, in exact integers; None for a column longer than 8"""
+    m = [[int(v) for v in row] for row in M]
+    n2 = max(m[0][0] ** 2 + m[1][0] ** 2, m[0][1] ** 2 + m[1][1] ** 2)
+    return next((K for K in (1, 2, 4, 8) if (K * AFFINE_ONE) ** 2 >= n2), None)
+
+
+def _check_affine_integers(M, what, name, face):
+    """one (2,3) integer matrix under include/gcfr.h's rules, or GcfrError"""
+    from . import _lib
+    m = [[int(v) for v in row] for row in M]
+    if m[0][0] * m[1][1] - m[0][1] * m[1][0] <= 0:
+        raise _lib.GcfrError("%s: %s of face %d has a determinant <= 0: a mirror image (which would need a mirrored light) or no map at all"
+                             % (what, name, face))
+    if affine_sub_samples(m) is None:
+        raise _lib.GcfrError("%s: %s of face %d has a column longer than %d: a step of one pixel crosses more than %d pixels"
+                             % (what, name, face, AFFINE_MAX_NORM, AFFINE_MAX_NORM))
+    if max(abs(m[0][2]), abs(m[1][2])) > AFFINE_MAX_SHIFT:
+        raise _lib.GcfrError("%s: %s of face %d has a translation beyond 2^26 pixels" % (what, name, face))
+
+
+def quantise_affine(net_to_photo):
+    """The integer pair the affine entries read, from one f64 matrix, on the host: `net_to_photo` (2,3) or (B,2,3), the map
+    (X, Y) = A (u, v, 1) from the network's continuous coordinates to the photograph's (pixel k covers [k, k+1) on both sides) ->
+    (F, I), int64 numpy arrays of that shape in units of 2^-14: F = rint(A 2^14), network -> photograph, and
+    I = rint(inverse(F / 2^14) 2^14), photograph -> network, the inverse of the QUANTISED F written out in f64 (det = a d - b c; the
+    linear part (d, -b; -c, a) / det; the translation -(linear part) t).  Refused with GcfrError: entries that are not finite, a
+    determinant <= 0 (a mirror image), a column of either matrix longer than 8, a translation beyond 2^26 pixels."""
+    from . import _lib
+    what = "quantise_affine"
+    try:
+        A = np.array(net_to_photo, dtype=np.float64)
+    except Exception as e:
+        raise _lib.GcfrError("%s: net_to_photo must be numbers (2,3) or (B,2,3): %s" % (what, e))
+    if A.shape[-2:] != (2, 3) or A.ndim not in (2, 3) or (A.ndim == 3 and A.shape[0] < 1):
+        raise _lib.GcfrError("%s: net_to_photo must be (2,3) or (B,2,3); got %s" % (what, A.shape))
+    if not np.isfinite(A).all() or np.abs(A).max() > 2.0 ** 27:
+        raise _lib.GcfrError("%s: net_to_photo must be finite, with no entry beyond 2^27" % what)
+    Fq = np.rint(A * AFFINE_ONE).astype(np.int64)
+    for b, m in enumerate(Fq.reshape(-1, 2, 3)):
+        _check_affine_integers(m, what, "F (network -> photograph)", b)
+    f = Fq.astype(np.float64) / AFFINE_ONE
+    a, b_, tx, c, d, ty = f[..., 0, 0], f[..., 0, 1], f[..., 0, 2], f[..., 1, 0], f[..., 1, 1], f[..., 1, 2]
+    det = a * d - b_ * c
+    i00, i01, i10, i11 = d / det, -b_ / det, -c / det, a / det
+    inv = np.stack([np.stack([i00, i01, -(i00 * tx + i01 * ty)], -1), np.stack([i10, i11, -(i10 * tx + i11 * ty)], -1)], -2)
+    if not np.isfinite(inv).all() or np.abs(inv).max() > 2.0 ** 27:
+        raise _lib.GcfrError("%s: the inverse map has an entry beyond 2^27" % what)
+    Iq = np.rint(inv * AFFINE_ONE).astype(np.int64)
+    for b, m in enumerate(Iq.reshape(-1, 2, 3)):
+        _check_affine_integers(m, what, "I (photograph -> network)", b)
+    return Fq, Iq
+
+
+def affine_from_rotated_box(cx, cy, bw, bh, angle_degrees, size):
+    """The map network -> photograph of a ROTATED face box, (2,3) f64 for `quantise_affine` and the affine entries: a box of
+    bw x bh photograph pixels centred at (cx, cy) and turned by `angle_degrees` about its centre, clockwise as the photograph is
+    displayed (+x right, +y down), over a network of `size` (h, w) (an int: square).  With angle 0 and (cx, cy) the centre of the box
+    (x0, y0, bw, bh) it is that box's axis-aligned map, (bw / w, 0, x0; 0, bh / h, y0)."""
+    from . import _lib
+    h, w = (size, size) if isinstance(size, int) else (tuple(size) if isinstance(size, (tuple, list)) and len(size) == 2 else (None, None))
+    if any(isinstance(n, bool) or not isinstance(n, int) or n < 1 for n in (h, w)):
+        raise _lib.GcfrError("affine_from_rotated_box: size must be the network's (h, w), positive integers; got %r" % (size,))
+    vals = np.array([cx, cy, bw, bh, angle_degrees], dtype=np.float64)
+    if vals.shape != (5,) or not np.isfinite(vals).all() or not (vals[2] > 0 and vals[3] > 0):
+        raise _lib.GcfrError("affine_from_rotated_box: cx, cy, bw > 0, bh > 0 and the angle must be finite numbers")
+    cx, cy, bw, bh, ang = vals.tolist()
+    quarter = ang / 90.0
+    if quarter == np.floor(quarter):                   # whole quarter turns: exact sines
+        co, si = ((1.0, 0.0), (0.0, 1.0), (-1.0, 0.0), (0.0, -1.0))[int(quarter) % 4]
+    else:
+        co, si = float(np.cos(np.radians(ang))), float(np.sin(np.radians(ang)))
+    sx, sy = bw / w, bh / h
+    A = np.array([[co * sx, -si * sy, 0.0], [si * sx, co * sy, 0.0]], np.float64)
+    A[:, 2] = np.array([cx, cy]) - A[:, :2] @ np.array([w / 2.0, h / 2.0])
+    return A
+
+
+def _affine_integers(net_to_photo, B, what):
+    """-> (F, I), contiguous (B,2,3) int64 numpy arrays under include/gcfr.h's rules, from what the affine entries take as the map:
+    an f64 matrix (2,3) | (B,2,3) network -> photograph (a list, a numpy array or a CPU tensor), which goes through
+    `quantise_affine`, or the INTEGER pair (F, I) of `quantise_affine`, each (2,3) | (B,2,3), which is taken unchanged"""
+    import torch
+    from . import _lib
+    host = lambda a: a.detach().numpy() if torch.is_tensor(a) else a
+    # (a pair: a tuple of two matrices; a tuple of two ROWS of numbers is one matrix)
+    is_pair = isinstance(net_to_photo, tuple) and len(net_to_photo) == 2 and all(torch.is_tensor(a) or np.ndim(a) >= 2 for a in net_to_photo)
+    parts = net_to_photo if is_pair else (net_to_photo,)
+    if any(torch.is_tensor(a) and a.is_cuda for a in parts):
+        raise _lib.GcfrError("%s: the map is HOST numbers (the entry bakes them into its launches); got a tensor on %s"
+                             % (what, next(a.device for a in parts if torch.is_tensor(a) and a.is_cuda)))
+    if is_pair:
+        pair = []
+        for name, a in zip(("F (network -> photograph)", "I (photograph -> network)"), net_to_photo):
+            try:
+                a = np.asarray(host(a))
+            except Exception as e:
+                raise _lib.GcfrError("%s: %s must be integers (2,3) or (B,2,3): %s" % (what, name, e))
+            if a.dtype.kind not in "iu":
+                raise _lib.GcfrError("%s: %s of a pair must be integers (quantise_affine's), got %s" % (what, name, a.dtype))
+            if a.shape not in ((2, 3), (B, 2, 3)):
+                raise _lib.GcfrError("%s: %s must be (2,3) or (%d,2,3); got %s" % (what, name, B, a.shape))
+            a = np.ascontiguousarray(np.broadcast_to(a.astype(np.int64), (B, 2, 3)))
+            for b, m in enumerate(a):
+                _check_affine_integers(m, what, name, b)
+            pair.append(a)
+        return tuple(pair)
+    try:
+        A = np.asarray(host(net_to_photo), dtype=np.float64)
+    except Exception as e:
+        raise _lib.GcfrError("%s: the map must be numbers (2,3) or (B,2,3): %s" % (what, e))
+    if A.shape not in ((2, 3), (B, 2, 3)):
+        raise _lib.GcfrError("%s: the map must be (2,3) or (%d,2,3) (network -> photograph); got %s" % (what, B, A.shape))
+    Fq, Iq = quantise_affine(A)
+    return tuple(np.ascontiguousarray(np.broadcast_to(a, (B, 2, 3))) for a in (Fq, Iq))
+
+
+def ingest_affine_device(photo_u8, net_to_photo, size):
+    """The network's input from a ROTATED face in each photograph, on the device: photo_u8 (B,Hp,Wp,3) uint8 of any size,
+    `net_to_photo` the HOST map from the network's coordinates to the photograph's -- an f64 matrix (2,3) for every face or (B,2,3)
+    (a list, a numpy array or a CPU tensor; `affine_from_rotated_box` builds one, a face aligner reports one), or the integer pair
+    (F, I) of `quantise_affine`, taken unchanged -- and `size` the network's (h, w) (an int: square) -> (B,h,w,3) f32 in [0,1].
+    Every network pixel samples the photograph bilinearly through the map at its centre, or at K x K sub-sample centres where a
+    step of one network pixel crosses more than one photograph pixel (K = 2, 4, 8), all in integers with 14 fractional bits: one
+    exact 64-bit sum, one f64 division, one rounding to f32 (include/gcfr.h states it; csrc/gcfr_fullres_affine.hip).  Taps beyond
+    the photograph's edge replicate it, so a face may hang over the edge.  For the axis-aligned map of a box at 1, 2, 4 or 8 times
+    the network's side these are `ingest_box_device`'s bits.  One launch per 32 faces, no host synchronisation; a malformed input
+    raises GcfrError before anything is loaded or launched."""
+    import torch
+    from . import _lib
+    what = "ingest_affine_device"
+    h, w = (size, size) if isinstance(size, int) else (tuple(size) if isinstance(size, (tuple, list)) and len(size) == 2 else (None, None))
+    B, Hp, Wp, _ = _check_photographs(photo_u8, 1, what, boxed=True)
+    if any(isinstance(n, bool) or not isinstance(n, int) or n < 1 for n in (h, w)) or h * w > 0x7fffffff:
+        raise _lib.GcfrError("%s: the network's size (h, w) must be positive integers with h w < 2^31; got %r" % (what, (h, w)))
+    Fq, _ = _affine_integers(net_to_photo, B, what)
+    _lib.require_device(photo_u8)
+    photo = photo_u8.detach().contiguous()
+    x_lo = torch.empty((B, h, w, 3), dtype=torch.float32, device=photo.device)
+    _lib.launch("gcfr_ingest_affine_u8", photo.device, photo, B, Hp, Wp, _host_pointer(Fq), h, w, x_lo, _lib.STREAM)
+    return x_lo
+
+
+def fullres_affine_composites_device(photo_u8, net_to_photo, x_lo, rendered, mask_u8, detail_clamp=4.0, floor=1.0, out=None):
+    """`fullres_box_composites_device` for a ROTATED face: photo_u8 (B,Hp,Wp,3) uint8 of any size; `net_to_photo` as in
+    `ingest_affine_device`; x_lo (B,h,w,3) f32, the network's input (`ingest_affine_device`); rendered (B,L,3,h,w) -> (B,L,Hp,Wp,3),
+    or (B,3,h,w) -> (B,Hp,Wp,3); mask_u8 (1|B,h,w) or (h,w) uint8, the compositing mask at the network's resolution IN THE NETWORK'S
+    FRAME.  A photograph pixel belongs to the face where its centre lands in the network square under the inverse map; there the
+    relit image, x_lo and the mask are carried to it bilinearly through that map (K x K sub-samples averaged where the face is
+    smaller than the network, K = 2, 4, 8; integer taps and weights, include/gcfr.h states every operation;
+    csrc/gcfr_fullres_affine.hip), and the quotient / detail transfer of `fullres_composites_device` follows.  Every other pixel is
+    the photograph's byte for every light: the entry always pastes, a rotated quad has no rectangular "box alone".  For the
+    axis-aligned map of a box at 1, 2 or 4 times the network's side these are `fullres_box_composites_device(paste=True)`'s bytes,
+    from this entry's own kernel: there is no dispatch between the two.  ONE launch per 32 faces for all L lights; the matrices
+    travel in the launch's arguments, nothing is uploaded.  `rendered` is the only operand that may be non-f32 on entry.  `out`: a
+    contiguous uint8 buffer of the result's shape that is written and returned; it must not overlap the photographs.  NOT
+    DIFFERENTIABLE.  No host synchronisation; a malformed input raises GcfrError before anything is loaded or launched."""
+    import torch
+    from . import _lib
+    what = "fullres_affine_composites_device"
+    _check_composite_tensors(what, x_lo, rendered, mask_u8, out)
+    if x_lo.dim() != 4 or x_lo.shape[-1] != 3 or min(x_lo.shape) < 1:
+        raise _lib.GcfrError("%s: x_lo must be (B,h,w,3); got %s" % (what, tuple(x_lo.shape)))
+    h, w = int(x_lo.shape[1]), int(x_lo.shape[2])
+    B, Hp, Wp, _ = _check_photographs(photo_u8, 1, what, boxed=True)
+    _, Iq = _affine_integers(net_to_photo, B, what)
+    photo, x, ren, m, L, shape = _composite_operands(what, photo_u8, x_lo, rendered, mask_u8, out, detail_clamp, floor, B, h, w, (Hp, Wp),
+                                                     frame=", in the network's frame")
+    if out is not None and out.data_ptr() < photo.data_ptr() + photo.numel() and photo.data_ptr() < out.data_ptr() + out.numel():
+        raise _lib.GcfrError("%s: out must not overlap the photographs" % what)
+    res = torch.empty(shape, dtype=torch.uint8, device=photo.device) if out is None else out
+    _lib.launch("gcfr_fullres_composites_affine_u8", photo.device, photo, x, ren, m, m.shape[0], B, L, Hp, Wp, _host_pointer(Iq), h, w,
+                float(floor), float(detail_clamp), res, _lib.STREAM)
     return res
 
 

@@ -856,6 +856,64 @@ int gcfr_fullres_composites_group_u8(const uint8_t *photo_u8, const float *x_lo,
                                      const int32_t *photo_index, int32_t h, int32_t w, float floor, float detail_clamp,
                                      uint8_t *out_u8, void *stream);
 
+/*
+ * ROTATED FACES (csrc/gcfr_fullres_affine.hip): the two ends for a face under a 2 x 3 AFFINE MAP -- the similarity a face aligner
+ * reports -- in the place of an axis-aligned box.  The ingest samples the photograph through the map into the network's input; the
+ * composite carries the L relit images back through the inverse map onto the photograph's own pixels, one launch for all lights.
+ *   photo_u8   (B,Hp,Wp,3) u8               the photographs, RGB, HWC
+ *   F, I       (B,2,3) int64, HOST          one map per face, row-major (M00, M01, M02, M10, M11, M12), in units of 2^-14
+ *                                           F: network -> photograph, (X, Y) = F (u, v, 1); I: photograph -> network
+ *   x_lo       (B,h,w,3) f32                the network's input: what gcfr_ingest_affine_u8 writes
+ *   rendered   (B,L,3,h,w) f32;  mask_u8 (mask_batch,h,w) u8 in the NETWORK'S frame, mask_batch = B or 1
+ *   out_u8     (B,L,Hp,Wp,3) u8 out         the photograph with the face relit; there is no "box alone"
+ * The entries take the matrices as GIVEN integers: the ingest reads only F, the composite reads only I; that the two are inverse
+ * to each other is the caller's business (postprocess.quantise_affine derives both from one f64 matrix).  F and I are HOST pointers
+ * like `boxes` above: read during the call, validated on the host and handed to the kernels by value, 32 faces per launch.
+ * All geometry is in INTEGERS, fixed point with 14 fractional bits, ONE = 2^14: no float decides a tap or a weight, and every value
+ * is rounded once.  Coordinates are continuous: pixel k covers [k, k+1) and its centre is k + 1/2, on both sides.
+ *   Sub-sampling.  For a matrix M, K(M) is the smallest of 1, 2, 4, 8 with K^2 ONE^2 >= max(M00^2 + M10^2, M01^2 + M11^2), an
+ *            integer comparison: how many sub-samples per axis a destination pixel takes when a step of one destination pixel
+ *            crosses more than one source pixel (the scales 1, 2, 4, 8 and the rule 8 nb >= n above).  Let den = 2 K ONE.
+ *            Destination pixel (x, y) has sub-samples (a, b) in [0, K)^2; sub-sample (a, b) has the source tap coordinate, already
+ *            shifted by the half pixel,
+ *              P0 = M00 (2Kx + 2a + 1) + M01 (2Ky + 2b + 1) + 2K M02 - K ONE,    P1 the same with row 1 of M,
+ *            exact in 64 bits, in units of 1 / den.
+ *   Ingest, K = K(F), per network pixel (column x = j, row y = i) and channel: S = the sum over the K^2 sub-samples (b outer, a
+ *            inner) and the four taps of each of wy wx byte, where x0 = floor(P0 / den), fx = P0 - x0 den, the taps are x0 and
+ *            x0 + 1 with weights den - fx and fx, and rows likewise with P1.  Tap indices are CLAMPED into the photograph
+ *            (replicate): a face may hang over the photograph's edge.  S < 255 x 64 x 2^36 = 2^50, so (double)S is exact;
+ *            x_lo = (float)((double)S / (255.0 K K (double)den (double)den)): one exact integer, one rounding.
+ *            For F = (s ONE, 0, x0 ONE; 0, s ONE, y0 ONE), s in {1, 2, 4, 8}, the bits are gcfr_ingest_box_u8's on the box
+ *            (x0, y0, s w, s h).
+ *   Inside test.  Photograph pixel (x, y) belongs to the face iff its centre lands in the network square:
+ *              c0 = I00 (2x+1) + I01 (2y+1) + 2 I02 lies in [0, 2 ONE w)  and  c1, with row 1, lies in [0, 2 ONE h).
+ *            Every other pixel is the photograph's byte for every light.
+ *   Carrier, K = K(I): applied to every channel of x_lo, to (float)mask_u8 / 255.0f and to every plane of `rendered`.  Per
+ *            sub-sample: U = max(P0, 0), j0 = min(U div den, w - 1), fu = U - (U div den) den, j1 = min(j0 + 1, w - 1),
+ *            tx = (float)((double)fu / (double)den), which is exact (den is a power of two, fu < 2^18); rows likewise with P1, h,
+ *            i0, i1, ty.  The sub-sample's value is Up's lerps in Up's order: a00 + tx (a01 - a00) on both rows, then
+ *            top + ty (bot - top).  With K = 1 that value is the carried value.  With K > 1 it is (float)(acc / (double)(K K)), acc
+ *            the f64 sum, starting from +0.0, with b outer and a inner, of (double)value.
+ *   Composite: inside, the p, xl, d, m, r, v above with the carrier in the place of Up, then byte = m > 0 ? saturate(rint((double)v))
+ *            : photo_u8 (the same device functions as gcfr_fullres_composites_u8).
+ *   Anchor, with no tolerance: with I the exact inverse of an axis-aligned F at s in {1, 2, 4} and integer x0, y0, every byte is
+ *            gcfr_fullres_composites_box_u8's (paste = 1) on that box: the taps, t and the clamps coincide.
+ * Refusals, each GCFR_ERR_INVALID_ARGUMENT before any launch: a NULL pointer (the matrix included); the pixel and chunk counts of
+ * the box entries (Hp Wp, h w < 2^31, B ceil(Hp Wp / 1024) < 2^31); for the matrix the entry reads: det = M00 M11 - M01 M10 <= 0 (no
+ * mirror image: a mirrored face would need a mirrored light), a column longer than 8 ONE, |M02| or |M12| > 2^40; everything
+ * gcfr_fullres_composites_u8 refuses of L, mask_batch, detail_clamp and floor; an out_u8 whose bytes overlap photo_u8's (the
+ * ingest: x_lo_out == photo_u8).  No gradient, no guided carrying, no perspective maps.
+ * Allocates nothing, never synchronises, may be captured into a graph.  Bit-equal to the numpy restatement
+ * (tests/fullres_affine_emulation.py).  Three dwords per four pixels when Wp is a multiple of 4 and out_u8 is 4-byte aligned, the
+ * copy outside the face included; one element at a time otherwise (same results).  The inside test, the taps, d and m are formed
+ * once per pixel, not once per light; with K > 1 the sub-samples' taps are recomputed per light.
+ */
+int gcfr_ingest_affine_u8(const uint8_t *photo_u8, int32_t B, int32_t Hp, int32_t Wp, const int64_t *F, int32_t h, int32_t w,
+                          float *x_lo_out, void *stream);
+int gcfr_fullres_composites_affine_u8(const uint8_t *photo_u8, const float *x_lo, const float *rendered, const uint8_t *mask_u8,
+                                      int32_t mask_batch, int32_t B, int32_t L, int32_t Hp, int32_t Wp, const int64_t *I, int32_t h,
+                                      int32_t w, float floor, float detail_clamp, uint8_t *out_u8, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Environment-map lighting: a lat-long radiance map integrated into the `rgb` (colour x weight per light) of the light-rig stage
  * above (csrc/gcfr_environment.hip).  Every texel belongs to the light direction nearest to it; a light's rgb is the
