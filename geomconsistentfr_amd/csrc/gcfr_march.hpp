@@ -516,6 +516,26 @@ enum { kModeInline = 0, kModeFull = 1, kModeRough = 2 };
 #ifndef GCFR_ROUGH_CHUNK_ARGMIN
 #define GCFR_ROUGH_CHUNK_ARGMIN 3   // ... five-wave training march
 #endif
+// The LDS annex.  The six-wave kernels are VALU-issue bound and have no register to keep a value they have
+// computed once; an LDS instruction is issued on its own port and takes no VALU slot.  The fused six-wave inference grid
+// kernels (PIPE) therefore PARK per-lane values in LDS where they are computed and read them back where the plain kernels
+// compute them again: a register annex addressed by (wave in workgroup, slot, lane) only -- no lane ever reads another
+// lane's slot, the waves of a workgroup never touch each other's planes, and a wave's LDS instructions are executed in
+// program order, so there is no barrier.  Not the retired LDS staging (round 3), which moved gathered DATA into LDS.
+#ifndef GCFR_LDS_PARK
+#define GCFR_LDS_PARK 1         // 0: nothing is parked, every kernel is the parent's (A/B: tools/build_variant.sh <name> -DGCFR_LDS_PARK=0)
+#endif
+typedef double f64x2 __attribute__((ext_vector_type(2)));
+constexpr int kParkSlots = 4;   // the sample positions of one group: 4 waves x 4 slots x 64 lanes x 16 B = 16 KiB per workgroup
+                                // (six workgroups per CU have 26 KiB each)
+// ONE allocation per kernel: declared inside march_tile every instantiation a kernel holds (all-ones masks or not) got its own
+// copy, 32 KiB, and the compiler gave up the six-wave target.  A kernel none of whose instantiations parks has no LDS from here.
+typedef f64x2 (*ParkPlane)[64];
+__device__ __forceinline__ ParkPlane park_annex(int wave)
+{
+    __shared__ f64x2 annex[4][kParkSlots][64];
+    return annex[GCFR_M(31, 0, wave & 3)];
+}
 template <int TILE_W, bool EVEN_HALF, bool WANT_ARGMIN, int DEPTH, bool FUSE_SHADE, int SPLIT, bool ALL_ONES = false, bool OWN = false,
           int MODE = kModeInline>
 __device__ __forceinline__ bool march_tile(ArgPtr a, const int bl, const int qy, const int tx,
@@ -550,6 +570,16 @@ __device__ __forceinline__ bool march_tile(ArgPtr a, const int bl, const int qy,
     // the group body as a rotating pair of texel gathers with the next group's prefetch behind it (see consume()): the six-wave
     // fused inference grid kernels
     constexpr bool PIPE = GCFR_BODY_PIPELINE && !WANT_ARGMIN && !KSPLIT && !ROUGH && FUSE_SHADE && DEPTH >= 2;
+    // the LDS annex (see park_annex): the sample positions the prefetch computes are parked for the main loop's bodies
+    // (EVEN_HALF only: with the annex the kernels of odd W/2 or H/2 spill -- 20 B per lane at 16 x 4 / groups of four, the first
+    //  group's bounds record stored in front of the main loop -- where the parent has no scratch; that parity keeps the parent's body)
+    // (all-ones masks, whose prefetch computes only the group's first and last position: those two are parked and the body computes
+    //  the middle ones -- +1.3 % on all-ones masks against an all-ones instantiation that parks nothing, profiles/lds_park_ab.txt)
+    constexpr bool PARK = GCFR_LDS_PARK && PIPE && EVEN_HALF;
+    static_assert(!PARK || DEPTH <= kParkSlots, "one slot per sample of a group");
+    ParkPlane park = nullptr;  // this wave's plane: [slot][lane]
+    if constexpr (PARK)
+        park = park_annex(wave);
     const int chunk = KSPLIT ? (a->N + 3) >> 2 : a->N;
     const int k_lo = KSPLIT ? wave * chunk : 0;
     const int N = KSPLIT ? min(a->N, k_lo + chunk) : a->N;  // exclusive upper bound ("N" below)
@@ -929,6 +959,18 @@ __device__ __forceinline__ bool march_tile(ArgPtr a, const int bl, const int qy,
         sx = x64 + tq[j] * dx64;  // T8:472 / 480 (f64, mul and add rounded separately)
         sy = y64 + tq[j] * dy64;
     };
+    // PARK: every position the prefetch computes is parked in the lane's slot j, and the main loop's body (issue(j) in consume())
+    // reads it back instead of computing it a second time from the same operands: the same two roundings, the same bits.
+    // ONE buffer is enough, and the order it relies on is program order within the wave: the prefetch that overwrites the slots
+    // is the body's late(), requested behind the LAST issue() of the group -- all reads of a group's slots precede the writes
+    // of the next group's -- and where a group has no body late() follows the decision directly and the parked values are
+    // dead.  The trailing loop never reads a slot (its leave path keeps the plain body and its own positions), so what the
+    // last prefetch of the main loop left behind -- the group behind the one that handed over, or behind the table's end,
+    // clamped -- is never used.
+    auto park_pos = [&](int j, double sx, double sy) {
+        if constexpr (PARK)
+            park[j][lane] = f64x2{sx, sy};
+    };
     auto prefetch = [&](Prefetched &p) {  // (the group whose table values tq holds)
         int cj[DEPTH], rj[DEPTH];
         if (ALL_ONES) {
@@ -938,8 +980,10 @@ __device__ __forceinline__ bool march_tile(ArgPtr a, const int bl, const int qy,
             if (use_zb) {
                 double px, py;
                 pos_tq(0, px, py);
+                park_pos(0, px, py);
                 (void)mask_offset(px, py, cj[0], rj[0]);
                 pos_tq(DEPTH - 1, px, py);
+                park_pos(DEPTH - 1, px, py);
                 (void)mask_offset(px, py, cj[DEPTH - 1], rj[DEPTH - 1]);
                 p.z = zb_fetch(cj[0], rj[0], cj[DEPTH - 1], rj[DEPTH - 1]);
             }
@@ -949,6 +993,7 @@ __device__ __forceinline__ bool march_tile(ArgPtr a, const int bl, const int qy,
         for (int j = 0; j < DEPTH; ++j) {
             double px, py;
             pos_tq(j, px, py);
+            park_pos(j, px, py);
             p.m[j] = buf_load_u8(mr, mask_offset(px, py, cj[j], rj[j]));
         }
         if (use_zb)
@@ -1181,8 +1226,17 @@ __device__ __forceinline__ bool march_tile(ArgPtr a, const int bl, const int qy,
             f32x4 qv[DEPTH];
             auto issue = [&](int j) {
                 constexpr bool CARRIED = FUSE_SHADE || WANT_ARGMIN;  // (see the plain body)
-                const double tj = (CARRIED && j == 0) ? ta64 : ((CARRIED && j == DEPTH - 1) ? tb64 : (double)tt[clampk(k0 + j)]);
-                const double sx = x64 + tj * dx64, sy = y64 + tj * dy64;  // T8:472 / 480 (mul and add rounded separately)
+                double sx, sy;
+                if (PARK && (!ALL_ONES || j == 0 || j == DEPTH - 1)) {
+                    // the position this group's prefetch computed and parked (see park_pos; all-ones masks: the first and the last only)
+                    const f64x2 s = park[GCFR_M(30, j ^ 1, j)][lane];
+                    sx = s.x;
+                    sy = s.y;
+                } else {
+                    const double tj = (CARRIED && j == 0) ? ta64 : ((CARRIED && j == DEPTH - 1) ? tb64 : (double)tt[clampk(k0 + j)]);
+                    sx = x64 + tj * dx64;  // T8:472 / 480 (mul and add rounded separately)
+                    sy = y64 + tj * dy64;
+                }
                 ux[j] = (sx + halfW) - 0.0001;  // unrounded position (T8:480-487)
                 uy[j] = (halfH - sy) - 0.0001;
                 const int fx = (int)__builtin_floor(ux[j]), fy = (int)__builtin_floor(uy[j]);  // may be -1: the quad grid has that row / column

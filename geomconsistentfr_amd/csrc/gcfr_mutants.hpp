@@ -48,6 +48,10 @@
 // 26  "every remaining sample of the lane lies outside the mask's box" (lane_last < next group's first sample)   off by one
 // 27  trailing loop: "the lane has left the box" (lane_last < this group's first sample)   off by one
 // 29  bound evaluated at the group's first AND last sample (linear in t)             first sample only
+// 30  LDS annex: the body reads sample j's parked position from slot j               from slot j ^ 1
+// 31  LDS annex: every wave of a workgroup has a plane of its own                    all four share plane 0
+//     (30 / 31 change no margin but an address: the parked sample positions of the six-wave fused inference grid kernels, DESIGN.md
+//      4.1g.  tests/test_gpu_march_lds_park.py is the suite they must fail; how many of its cases each fails: profiles/lds_park_ab.txt.)
 //
 // 3 and 5 are the two mutants no END-TO-END test kills (profiles/r05_mutants.md): K1, K2 r and the plane term budget for three different
 // effects -- the 1e-4 position offset times |BCz|, the f32 roundings of the distance's products, the offset times the surface's slope --
@@ -117,3 +121,5 @@
 #define GCFR_MUT_PAIR_26_26 ~, 1
 #define GCFR_MUT_PAIR_27_27 ~, 1
 #define GCFR_MUT_PAIR_29_29 ~, 1
+#define GCFR_MUT_PAIR_30_30 ~, 1
+#define GCFR_MUT_PAIR_31_31 ~, 1
