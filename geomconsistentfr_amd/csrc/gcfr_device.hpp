@@ -32,6 +32,16 @@ __device__ inline uint32_t buf_load_u8(__amdgpu_buffer_rsrc_t r, int byte_off)
 {
     return __builtin_amdgcn_raw_buffer_load_b8(r, byte_off, 0, 0);
 }
+// The bilinear weights of position u (T8:492-494: w0 = ceil(u) - u, w1 = u - floor(u)) as two v_fract_f64 -- the negation is a
+// source modifier -- instead of floor, ceil and two subtractions.  The same bits for every finite u except 0 < |u| <= 2^-54, where
+// IEEE rounds 1 -+ |u| to 1.0 and the instruction clamps to 1 - 2^-53: a window no sample position of an image of six or more
+// rows and columns can reach (tests/test_fract_weights_host.py has the argument, tests/test_gpu_fract_weights.py the instruction;
+// DESIGN.md 4.1h).  Callers: the bounds variant of the fused inference grid march only (gcfr_march.hpp, FRACT).
+__device__ inline void bilinear_weights(double u, double &w0, double &w1)
+{
+    w0 = __builtin_amdgcn_fract(-u);
+    w1 = __builtin_amdgcn_fract(u);
+}
 
 // census: end point (T8:378-465) + ray constants
 // Image box in image-plane coordinates (T8:386-387, 416, 399).

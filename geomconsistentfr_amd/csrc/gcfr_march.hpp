@@ -525,6 +525,13 @@ enum { kModeInline = 0, kModeFull = 1, kModeRough = 2 };
 #ifndef GCFR_LDS_PARK
 #define GCFR_LDS_PARK 1         // 0: nothing is parked, every kernel is the parent's (A/B: tools/build_variant.sh <name> -DGCFR_LDS_PARK=0)
 #endif
+// The bilinear weights as two v_fract_f64 per axis (bilinear_weights()): the bounds variant (MODE == kModeFull) of
+// the fused six-wave inference grid kernels only (FRACT in march_tile) -- the rough sibling, the training and march-only grid kernels,
+// the k-split kernels, ray_sample, the plain kernel and the backward keep floor / ceil / two subtractions.  Images with fewer than six
+// rows or columns never march in the bounds variant of those kernels (see use_zb).
+#ifndef GCFR_FRACT_WEIGHTS
+#define GCFR_FRACT_WEIGHTS 1    // 0: every kernel keeps the parent's weights (A/B: tools/build_variant.sh <name> -DGCFR_FRACT_WEIGHTS=0)
+#endif
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 constexpr int kParkSlots = 4;   // the sample positions of one group: 4 waves x 4 slots x 64 lanes x 16 B = 16 KiB per workgroup
                                 // (six workgroups per CU have 26 KiB each)
@@ -577,6 +584,13 @@ __device__ __forceinline__ bool march_tile(ArgPtr a, const int bl, const int qy,
     //  the middle ones -- +1.3 % on all-ones masks against an all-ones instantiation that parks nothing, profiles/lds_park_ab.txt)
     constexpr bool PARK = GCFR_LDS_PARK && PIPE && EVEN_HALF;
     static_assert(!PARK || DEPTH <= kParkSlots, "one slot per sample of a group");
+    // the weights from v_fract_f64 (see GCFR_FRACT_WEIGHTS): every body of the bounds variant of the FUSED six-wave inference grid
+    // kernels, PIPE or plain (groups of one), main loop or leave path.  Not the march-only six-wave kernels (!FUSE_SHADE: one register
+    // short as they are -- see CARRIED in the body --, the even half-parity one at 16 x 4 / groups of four is re-planned into 12 B of
+    // scratch per lane with it) and not the five-wave training kernels (WANT_ARGMIN: built and measured -- two to four VGPRs fewer, and
+    // the training march on an untrained network's depth, which runs their untouched rough loop, 0.25 % SLOWER, beyond the parent's
+    // spread: profiles/fract_weights_ab.txt): both keep the parent's body, instruction for instruction.
+    constexpr bool FRACT = GCFR_FRACT_WEIGHTS && MODE == kModeFull && FUSE_SHADE && !WANT_ARGMIN;
     ParkPlane park = nullptr;  // this wave's plane: [slot][lane]
     if constexpr (PARK)
         park = park_annex(wave);
@@ -669,7 +683,10 @@ __device__ __forceinline__ bool march_tile(ArgPtr a, const int bl, const int qy,
 // census: give-up test (incl. nrm, c1)
     const ConstI32Ptr tfl = (ConstI32Ptr)(unsigned long long)a->tflag;  // the prepass' record about the sample table (scalar loads)
     const bool t_increasing = (a->N >= 2) && (tfl[kTfOk] != 0);  // checked by the prepass (see its table check)
-    bool use_zb = !ROUGH && (a->zb != nullptr) && t_increasing;
+    // (FRACT: an image of fewer than six rows or columns can put a position inside 0 < |u| <= 2^-54, the one window where the fract
+    //  weights are not the reference's -- |s| in [0.5, 2) -- and is marched by the rough sibling, whose weights are: one scalar
+    //  compare per tile, nothing in any sample loop)
+    bool use_zb = !ROUGH && (a->zb != nullptr) && t_increasing && !(FRACT && (H < 6 || W < 6));
     if (MODE == kModeFull && !use_zb)
         return true;  // (wave-uniform: facts about the launch) marched by the rough variant
     const int zrec = tfl[kTfStride];
@@ -1084,10 +1101,22 @@ __device__ __forceinline__ bool march_tile(ArgPtr a, const int bl, const int qy,
     // One sample's arithmetic behind its texel gather: bilinear depth (T8:480-494, f64), point A (T8:497-502), the squared
     // distance numerator (T8:503-509, f32, torch.cross's fma placement) and the running minimum with its tie predecessor.
     // Shared by the group bodies and the rough loop, so both evaluate the reference's rounding sequence with the same code.
+    // The weights (T8:492-494).  Parent's form: w0 = ceil(u) - u, w1 = u - floor(u), the floors handed in (fxj, fyj).  FRACT:
+    // w1 = v_fract_f64(u), w0 = v_fract_f64(-u), the floors unused.  v_fract_f64(u) = min(rn(u - floor(u)), 1 - 2^-53); for u >= 0,
+    // w1 is the parent's subtraction and w0 = rn(-u - floor(-u)) = rn(ceil(u) - u); for u < 0 likewise with the roles exchanged; an
+    // integral u gives 0 and 0 in both forms.  The clamp binds only where rn(1 - |u|) = 1, i.e. 0 < |u| <= 2^-54, and u = (s + W/2)
+    // - 0.0001 with s + W/2 exact near u = 0 (Sterbenz) and a multiple of ulp(s): |u| >= the distance of the double 0.0001 to that
+    // grid, which is >= 2.1e-16 > 2^-54 for |s| >= 2, i.e. for W/2 >= 3 (uy = (H/2 - sy) - 0.0001 likewise).  Smaller images: use_zb.
+    // (The floors are handed in by every caller, as in the parent; under FRACT they are unused and, with them, whatever computed them.)
     auto eval_sample = [&](int k, bool masked, double uxj, double uyj, double fxj, double fyj, const f32x4 &q) {
-        const double gxd = __builtin_ceil(uxj), gyd = __builtin_ceil(uyj);
-        const double wx0 = gxd - uxj, wx1 = uxj - fxj;
-        const double wy0 = gyd - uyj, wy1 = uyj - fyj;
+        double wx0, wx1, wy0, wy1;
+        if constexpr (FRACT) {
+            bilinear_weights(uxj, GCFR_M(32, wx1, wx0), GCFR_M(32, wx0, wx1));
+            bilinear_weights(uyj, wy0, wy1);
+        } else {
+            wx0 = __builtin_ceil(uxj) - uxj, wx1 = uxj - fxj;
+            wy0 = __builtin_ceil(uyj) - uyj, wy1 = uyj - fyj;
+        }
         const double zUL = q.x, zUR = q.y, zLL = q.z, zLR = q.w;
         const double up = zUL * wx0 + zUR * wx1;
         const double low = zLL * wx0 + zLR * wx1;
@@ -1189,7 +1218,7 @@ __device__ __forceinline__ bool march_tile(ArgPtr a, const int bl, const int qy,
                 const double sx = x64 + tj * dx64, sy = y64 + tj * dy64;  // T8:472 / 480 (mul and add rounded separately)
                 ux[j] = (sx + halfW) - 0.0001;  // unrounded position (T8:480-487)
                 uy[j] = (halfH - sy) - 0.0001;
-                fxd[j] = __builtin_floor(ux[j]);
+                fxd[j] = __builtin_floor(ux[j]);  // (FRACT: the floors serve the address only and are dead across the gather)
                 fyd[j] = __builtin_floor(uy[j]);
                 const int fx = (int)fxd[j], fy = (int)fyd[j];  // may be -1: the quad grid has that row / column
                 const int texel = __mul24(fy, Wp) + fx;
@@ -1243,7 +1272,8 @@ __device__ __forceinline__ bool march_tile(ArgPtr a, const int bl, const int qy,
                 const int texel = __mul24(fy, Wp) + fx;
                 qv[j] = __builtin_bit_cast(
                     f32x4, __builtin_amdgcn_raw_buffer_load_b128(qr, (texel << 4) + quad_origin, 0, 0));
-                asm volatile("" : "+v"(ux[j]), "+v"(uy[j]));
+                if constexpr (!FRACT)  // (FRACT: no floor is consumed behind the flight, so there is nothing to keep from being carried)
+                    asm volatile("" : "+v"(ux[j]), "+v"(uy[j]));
             };
             issue(0);
             if (DEPTH > 1)

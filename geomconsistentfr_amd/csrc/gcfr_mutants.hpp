@@ -52,6 +52,9 @@
 // 31  LDS annex: every wave of a workgroup has a plane of its own                    all four share plane 0
 //     (30 / 31 change no margin but an address: the parked sample positions of the six-wave fused inference grid kernels, DESIGN.md
 //      4.1g.  tests/test_gpu_march_lds_park.py is the suite they must fail; how many of its cases each fails: profiles/lds_park_ab.txt.)
+// 32  fract weights: wx0 = v_fract_f64(-ux), wx1 = v_fract_f64(ux)                  exchanged
+//     (32 changes no margin either: the bilinear weights of the bounds variant of the fused inference grid kernels, DESIGN.md 4.1h.
+//      tests/test_gpu_march_fract_weights.py is the suite it must fail; how many of its cases it fails: profiles/fract_weights_ab.txt.)
 //
 // 3 and 5 are the two mutants no END-TO-END test kills (profiles/r05_mutants.md): K1, K2 r and the plane term budget for three different
 // effects -- the 1e-4 position offset times |BCz|, the f32 roundings of the distance's products, the offset times the surface's slope --
@@ -123,3 +126,4 @@
 #define GCFR_MUT_PAIR_29_29 ~, 1
 #define GCFR_MUT_PAIR_30_30 ~, 1
 #define GCFR_MUT_PAIR_31_31 ~, 1
+#define GCFR_MUT_PAIR_32_32 ~, 1

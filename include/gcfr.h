@@ -159,7 +159,10 @@ int gcfr_light_prep(const float *light_raw, int32_t n, int32_t clamp_z, float cl
  *               maxima of the depth an unmasked sample can read ("horizon tables", shapes with W % 4 == 0 and
  *               H, W <= 1024), against which a ray that has passed its last candidate stops marching; results are
  *               bit-identical to the NULL-workspace path, only faster.  Contents are scratch: rewritten by every
- *               call, nothing in it needs initialising.
+ *               call, nothing in it needs initialising.  Images with H < 6 or W < 6 are marched WITHOUT the depth
+ *               bounds by the grid kernels (the same bits; at most four rows or columns of work): the bounds variant
+ *               takes its bilinear weights from v_fract_f64, which is the reference's arithmetic only where no sample
+ *               position can fall inside 0 < |u| <= 2^-54 -- every image of six or more rows and columns.
  * Supported: 2 <= H,W <= 4096, even; 1 <= N <= 4096.
  */
 size_t gcfr_shadow_workspace_bytes(int32_t B, int32_t H, int32_t W);
