@@ -123,6 +123,8 @@ _SIGNATURES = {
     "gcfr_fullres_composites_group_u8": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _i, _i, _f, _f, _p, _p]),
     "gcfr_ingest_affine_u8": (_i, [_p, _i, _i, _i, _p, _i, _i, _p, _p]),
     "gcfr_fullres_composites_affine_u8": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _i, _i, _f, _f, _p, _p]),
+    "gcfr_ingest_group_affine_u8": (_i, [_p, _i, _i, _i, _p, _p, _i, _i, _i, _p, _p]),
+    "gcfr_fullres_composites_group_affine_u8": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _i, _i, _f, _f, _p, _p]),
     "gcfr_environment_cells": (_i, [_p, _p, _p, _i, _i, _i, _f, _p, _p]),
     "gcfr_environment_fwd": (_i, [_p, _i, _i, _i, _p, _p, _i, _p, _p]),
     "gcfr_environment_bwd": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _p]),

@@ -25,7 +25,7 @@ SOURCES = ["gcfr_shadow.hip", "gcfr_shade.hip", "gcfr_backward.hip", "gcfr_norma
            "gcfr_dataset.hip", "gcfr_losses.hip", "gcfr_supervised_losses.hip", "gcfr_light_rig.hip", "gcfr_environment.hip",
            "gcfr_light_fit.hip", "gcfr_rig_frames.hip", "gcfr_fullres.hip", "gcfr_fullres_guided.hip",
            "gcfr_fullres_box.hip", "gcfr_fullres_box_guided.hip", "gcfr_fullres_anybox.hip", "gcfr_fullres_group.hip",
-           "gcfr_fullres_affine.hip"]
+           "gcfr_fullres_affine.hip", "gcfr_fullres_group_affine.hip"]
 MARCH_UNIT = "gcfr_march_unit.hip"
 # (tile width, samples per group): the default shape first
 MARCH_UNITS = [(16, 4), (16, 2), (16, 1), (8, 4), (8, 2), (8, 1), (32, 4), (32, 2), (32, 1), (64, 4), (64, 2), (64, 1)]

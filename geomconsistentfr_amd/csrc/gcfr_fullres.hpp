@@ -22,6 +22,8 @@
 // gcfr_fullres_affine.hip (a rotated face under a 2 x 3 affine map) is a seventh: the same arithmetic, vector-path pieces,
 // composite_pixel (over its own carrier, AffineCarrier), per-face pieces, box_shape and fullres_operands; its maps travel in a
 // block of its own (AffineArgs) with kBoxFaces faces per launch.
+// gcfr_fullres_group_affine.hip (every TILTED face of a photograph in one launch) is an eighth: that carrier and those maps
+// (gcfr_fullres_affine.hpp) over the same arithmetic, with the running bytes in the place of the photograph's.
 #pragma once
 
 #include <type_traits>

@@ -567,6 +567,83 @@ def relight_rig_in_group_photograph(model, photos_u8, boxes, photo_index, mask_u
                                                   composite_mask_u8, epoch, detail_clamp, floor).cpu().numpy()
 
 
+def _group_affine_entry(photos_u8, net_to_photo, photo_index, lights, light_frame, device):
+    """what the four group-affine entries do before the pass: the photographs on the device, the host indices checked, the host map
+    as `quantise_affine`'s integer pair, quantised ONCE for the ingest, the composite and the lights, and the lights in the faces'
+    frame"""
+    if light_frame not in LIGHT_FRAMES:
+        raise GcfrError("light_frame must be one of %s; got %r" % (LIGHT_FRAMES, light_frame))
+    _check_host_photo_index(photo_index)
+    photos = _as_photographs(photos_u8, device)
+    what = "relight_in_group_photograph_affine"
+    pi = pp._check_photo_index(photo_index, photos, what, faces=pp._faces_of_map(net_to_photo) if photo_index is None else None)
+    pair = pp._affine_integers(net_to_photo, int(pi.shape[0]), what)
+    if light_frame == "photograph":
+        lights = lights_in_face_frame(lights, pair[1], int(pi.shape[0]))
+    return photos, pair, pi, lights
+
+
+@torch.no_grad()
+def relight_lights_in_group_photograph_affine_device(model, photos_u8, net_to_photo, photo_index, mask_u8, lights, ambient: float = 0.5,
+                                                     focal: float = None, device="cuda", composite_mask_u8=None, epoch: int = 200,
+                                                     detail_clamp: float = 4.0, floor: float = 1.0,
+                                                     light_frame: str = "face") -> torch.Tensor:
+    """`relight_lights_in_group_photograph_affine` up to the bytes ON THE DEVICE: (P,L,Hp,Wp,3) uint8 tensor, nothing copied back.
+    `photos_u8` / `mask_u8` / `lights` may already be device tensors; `net_to_photo` and `photo_index` stay on the host."""
+    photos, pair, pi, lights = _group_affine_entry(photos_u8, net_to_photo, photo_index, lights, light_frame, device)
+    return _relight_photographs(model, photos, mask_u8, lights, ambient, focal, device, composite_mask_u8, epoch,
+                                lambda ph: pp.ingest_group_affine_device(ph, pair, pi, _network_size(mask_u8)),
+                                lambda ph, *a: pp.fullres_group_affine_composites_device(ph, pair, pi, *a, detail_clamp, floor))
+
+
+@torch.no_grad()
+def relight_lights_in_group_photograph_affine(model, photos_u8, net_to_photo, photo_index, mask_u8, lights, ambient: float = 0.5,
+                                              focal: float = None, device="cuda", composite_mask_u8=None, epoch: int = 200,
+                                              detail_clamp: float = 4.0, floor: float = 1.0, light_frame: str = "face") -> np.ndarray:
+    """EVERY TILTED face of a GROUP PHOTOGRAPH relit: photos_u8 (P,Hp,Wp,3) uint8 (or one (Hp,Wp,3)), B faces with the host map
+    `net_to_photo` (B,2,3) f64 -- what a face aligner reports per head; (2,3) for every face; or `postprocess.quantise_affine`'s
+    integer pair (`relight_lights_in_photograph_affine`'s rules) -- and host `photo_index` (B,) naming each face's photograph (any
+    order; a photograph may have no face, one or many; None: all faces in the one photograph) -> (P,L,Hp,Wp,3) uint8 RGB: every
+    photograph under every one of `lights` with ALL of its faces relit inside their tilted quads.  Three steps on the device:
+    `postprocess.ingest_group_affine_device` (the photographs are not copied per face), ONE `forward_lights` pass on all B faces,
+    then `postprocess.fullres_group_affine_composites_device`: one pass over each photograph's bytes, per photograph the chain of
+    `relight_lights_in_photograph_affine`'s composite over its faces in ascending face index (see
+    `relight_lights_in_group_photograph` for overlapping faces).  The matrix is quantised once per call.  `mask_u8` /
+    `composite_mask_u8` are in the network's frame and shared by the faces.  `light_frame` as in
+    `relight_lights_in_photograph_affine`: "photograph" turns each FACE's copy of the lights by its own map, which is what makes
+    "light from the photograph's left" mean the same thing on every head of the group.  One device-to-host copy of the result at the
+    end."""
+    return relight_lights_in_group_photograph_affine_device(model, photos_u8, net_to_photo, photo_index, mask_u8, lights, ambient, focal,
+                                                            device, composite_mask_u8, epoch, detail_clamp, floor,
+                                                            light_frame).cpu().numpy()
+
+
+@torch.no_grad()
+def relight_rig_in_group_photograph_affine_device(model, photos_u8, net_to_photo, photo_index, mask_u8, lights, light_rgb,
+                                                  ambient: float = 0.5, focal: float = None, device="cuda", composite_mask_u8=None,
+                                                  epoch: int = 200, detail_clamp: float = 4.0, floor: float = 1.0,
+                                                  light_frame: str = "face") -> torch.Tensor:
+    """`relight_rig_in_group_photograph_affine` up to the bytes ON THE DEVICE: (P,Hp,Wp,3) uint8 tensor, nothing copied back."""
+    photos, pair, pi, lights = _group_affine_entry(photos_u8, net_to_photo, photo_index, lights, light_frame, device)
+    return _relight_photographs(model, photos, mask_u8, lights, ambient, focal, device, composite_mask_u8, epoch,
+                                lambda ph: pp.ingest_group_affine_device(ph, pair, pi, _network_size(mask_u8)),
+                                lambda ph, *a: pp.fullres_group_affine_composites_device(ph, pair, pi, *a, detail_clamp, floor),
+                                light_rgb, rig=True)
+
+
+@torch.no_grad()
+def relight_rig_in_group_photograph_affine(model, photos_u8, net_to_photo, photo_index, mask_u8, lights, light_rgb, ambient: float = 0.5,
+                                           focal: float = None, device="cuda", composite_mask_u8=None, epoch: int = 200,
+                                           detail_clamp: float = 4.0, floor: float = 1.0, light_frame: str = "face") -> np.ndarray:
+    """`relight_rig` on every tilted face of a group photograph (`relight_lights_in_group_photograph_affine`, `light_frame`
+    included): ONE (P,Hp,Wp,3) uint8 RGB composite per photograph under the rig of `lights` with colour x weight `light_rgb`, all of
+    its faces relit; with one light of colour 1 it equals `relight_lights_in_group_photograph_affine(...)[:, 0]`.  One device-to-host
+    copy at the end."""
+    return relight_rig_in_group_photograph_affine_device(model, photos_u8, net_to_photo, photo_index, mask_u8, lights, light_rgb, ambient,
+                                                         focal, device, composite_mask_u8, epoch, detail_clamp, floor,
+                                                         light_frame).cpu().numpy()
+
+
 def _rig_frames(x, out, cm, light_rgb_frames, transfer: bool, fix_border: bool) -> torch.Tensor:
     """`forward_lights`' tuple -> (B,F,H,W,3) uint8: ONE rig-frames launch on its albedo (out[0]) and final shading (out[8]), and
     the optional border fix on the (B F,H,W,3) view"""

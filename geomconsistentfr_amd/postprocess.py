@@ -23,6 +23,9 @@ Device path (HIP kernels of csrc/gcfr_postprocess.hip, no CPU fallback): `infere
                                 the network's f32 input, csrc/gcfr_fullres_affine.hip
   fullres_affine_composites_device  the relit images carried back through the inverse map onto the photograph's pixels
   quantise_affine, affine_from_rotated_box   (host) the integer matrices those two read; the map of a rotated box
+  ingest_group_affine_device    `ingest_affine_device` for B tilted faces spread over P photographs,
+                                csrc/gcfr_fullres_group_affine.hip
+  fullres_group_affine_composites_device   every tilted face of a photograph relit in ONE pass over it
 
 Host side: the on-disk formats of load_data() (T8:545-556).  The numpy statements of the script lines these kernels
 implement live in oracle/postprocess_statements.py (test infrastructure, pinned to the reference's own main() by
@@ -670,6 +673,84 @@ def fullres_affine_composites_device(photo_u8, net_to_photo, x_lo, rendered, mas
     res = torch.empty(shape, dtype=torch.uint8, device=photo.device) if out is None else out
     _lib.launch("gcfr_fullres_composites_affine_u8", photo.device, photo, x, ren, m, m.shape[0], B, L, Hp, Wp, _host_pointer(Iq), h, w,
                 float(floor), float(detail_clamp), res, _lib.STREAM)
+    return res
+
+
+def _faces_of_map(net_to_photo):
+    """how many faces the map of an affine entry names by itself: B of a (B,2,3) matrix (or of the F of an integer pair), else 1"""
+    import torch
+    a = net_to_photo
+    if isinstance(a, tuple) and len(a) == 2 and all(torch.is_tensor(x) or np.ndim(x) >= 2 for x in a):
+        a = a[0]
+    try:
+        shape = tuple(a.shape) if torch.is_tensor(a) else np.shape(a)
+    except Exception:
+        shape = ()
+    return int(shape[0]) if len(shape) == 3 and shape[0] >= 1 else 1
+
+
+def ingest_group_affine_device(photo_u8, net_to_photo, photo_index, size):
+    """`ingest_affine_device` for a GROUP PHOTOGRAPH: photo_u8 (P,Hp,Wp,3) uint8, B tilted faces with the host map `net_to_photo` --
+    (B,2,3) f64 (or (2,3) for every face), or `quantise_affine`'s integer pair, as that entry takes it -- and host `photo_index` (B,)
+    naming each face's photograph, as `ingest_group_device` takes it (any order; a photograph may have no face, one or many; None:
+    every face in the one photograph, P == 1) -> (B,h,w,3) f32 in [0,1].  The bits are
+    `ingest_affine_device(photo_u8[photo_index], net_to_photo, size)`'s, and the photographs are neither gathered nor copied
+    (include/gcfr.h states it; csrc/gcfr_fullres_group_affine.hip).  One launch per 32 faces, no host synchronisation; a malformed
+    input raises GcfrError before anything is loaded or launched."""
+    import torch
+    from . import _lib
+    what = "ingest_group_affine_device"
+    h, w = (size, size) if isinstance(size, int) else (tuple(size) if isinstance(size, (tuple, list)) and len(size) == 2 else (None, None))
+    pi = _check_photo_index(photo_index, photo_u8, what, faces=_faces_of_map(net_to_photo) if photo_index is None else None)
+    B = int(pi.shape[0])
+    P, Hp, Wp, _ = _check_photographs(photo_u8, 1, what, boxed=True)
+    if any(isinstance(n, bool) or not isinstance(n, int) or n < 1 for n in (h, w)) or h * w > 0x7fffffff:
+        raise _lib.GcfrError("%s: the network's size (h, w) must be positive integers with h w < 2^31; got %r" % (what, (h, w)))
+    Fq, _ = _affine_integers(net_to_photo, B, what)
+    _lib.require_device(photo_u8)
+    photo = photo_u8.detach().contiguous()
+    x_lo = torch.empty((B, h, w, 3), dtype=torch.float32, device=photo.device)
+    _lib.launch("gcfr_ingest_group_affine_u8", photo.device, photo, P, Hp, Wp, _host_pointer(Fq), _host_pointer(pi), B, h, w, x_lo,
+                _lib.STREAM)
+    return x_lo
+
+
+def fullres_group_affine_composites_device(photo_u8, net_to_photo, photo_index, x_lo, rendered, mask_u8, detail_clamp=4.0, floor=1.0,
+                                           out=None):
+    """EVERY TILTED face of a photograph relit in one pass over the photograph: photo_u8 (P,Hp,Wp,3) uint8; `net_to_photo` and
+    `photo_index` as in `ingest_group_affine_device`; x_lo (B,h,w,3) f32, the network's input (`ingest_group_affine_device`); rendered
+    (B,L,3,h,w) -> (P,L,Hp,Wp,3), or (B,3,h,w) -> (P,Hp,Wp,3); mask_u8 (1|B,h,w) or (h,w) uint8, per FACE and in the network's frame,
+    exactly as `fullres_affine_composites_device` takes them.  Per photograph and light the result is the CHAIN of that entry's
+    composite over the photograph's faces in ascending face index, byte for byte: the running image starts as the photograph; a face
+    relights it where a pixel's centre lands in the network square under its map and its carried mask is positive, reading the
+    running bytes where that entry reads the photograph's, and every step rounds to a byte (include/gcfr.h states it;
+    csrc/gcfr_fullres_group_affine.hip).  Where at most one face relights a pixel the byte is that entry's; where two do, the second
+    face's gain multiplies the first's result, so order matters there and nowhere else.  A photograph without faces comes back as it
+    is for every light; all faces of a photograph share the light index.  With `photo_index = arange(B)` and P = B these are
+    `fullres_affine_composites_device`'s bytes; with axis-aligned maps at 1, 2 or 4 times the network's side they are
+    `fullres_group_composites_device`'s on the same boxes.  ONE launch per 32 faces, whole photographs per launch; a photograph with
+    more than 32 faces is continued by further launches on the same stream.  `out`: a contiguous uint8 buffer of the result's shape
+    that is written and returned; it must not overlap the photographs.  NOT DIFFERENTIABLE.  No host synchronisation; a malformed
+    input raises GcfrError before anything is loaded or launched."""
+    import torch
+    from . import _lib
+    what = "fullres_group_affine_composites_device"
+    _check_composite_tensors(what, x_lo, rendered, mask_u8, out)
+    if x_lo.dim() != 4 or x_lo.shape[-1] != 3 or min(x_lo.shape) < 1:
+        raise _lib.GcfrError("%s: x_lo must be (B,h,w,3); got %s" % (what, tuple(x_lo.shape)))
+    B, h, w = int(x_lo.shape[0]), int(x_lo.shape[1]), int(x_lo.shape[2])
+    pi = _check_photo_index(photo_index, photo_u8, what, faces=B)
+    P, Hp, Wp, _ = photo_u8.shape
+    _, Iq = _affine_integers(net_to_photo, B, what)
+    # (a photograph that is not contiguous is copied below and cannot overlap anything; where the tensors live is the last check)
+    if (out is not None and photo_u8.is_contiguous() and out.data_ptr() < photo_u8.data_ptr() + photo_u8.numel()
+            and photo_u8.data_ptr() < out.data_ptr() + out.numel()):
+        raise _lib.GcfrError("%s: out must not overlap the photographs" % what)
+    photo, x, ren, m, L, shape = _composite_operands(what, photo_u8, x_lo, rendered, mask_u8, out, detail_clamp, floor, B, h, w, (Hp, Wp),
+                                                     frame=", in the network's frame", images=P)
+    res = torch.empty(shape, dtype=torch.uint8, device=photo.device) if out is None else out
+    _lib.launch("gcfr_fullres_composites_group_affine_u8", photo.device, photo, x, ren, m, m.shape[0], P, B, L, Hp, Wp, _host_pointer(Iq),
+                _host_pointer(pi), h, w, float(floor), float(detail_clamp), res, _lib.STREAM)
     return res
 
 

@@ -917,6 +917,63 @@ int gcfr_fullres_composites_affine_u8(const uint8_t *photo_u8, const float *x_lo
                                       int32_t mask_batch, int32_t B, int32_t L, int32_t Hp, int32_t Wp, const int64_t *I, int32_t h,
                                       int32_t w, float floor, float detail_clamp, uint8_t *out_u8, void *stream);
 
+/*
+ * ROTATED FACES IN GROUP PHOTOGRAPHS (csrc/gcfr_fullres_group_affine.hip): every tilted face of a photograph relit in one pass over
+ * the photograph's bytes.  The group entries above take only axis-aligned boxes; the affine entries above take one face per
+ * photograph and return one photograph per face.  Here B >= 1 faces, each under its own pair of maps, are spread over P photographs
+ * and ONE photograph per photograph comes back.
+ *   photo_u8     (P,Hp,Wp,3) u8
+ *   F, I         (B,2,3) int64 HOST, one pair per face under gcfr_ingest_affine_u8's rules: row-major, in units of 2^-14 (ONE =
+ *                2^14); det > 0; no column longer than 8 ONE; |M02|, |M12| <= 2^40.  The ingest reads only F, the composite only I.
+ *   photo_index  (B,) i32 HOST, 0 <= photo_index[b] < P: the photograph of face b.  Any order; a photograph may have no face, one
+ *                face or many, more than 32 included.  Read during the call like the maps, and handed to the kernels by value.
+ *   x_lo         (B,h,w,3) f32;  rendered (B,L,3,h,w) f32;  mask_u8 (mask_batch,h,w) u8, mask_batch in {1, B}: per FACE, in the
+ *                network's frame, exactly as gcfr_fullres_composites_affine_u8 takes them
+ *   out_u8       (P,L,Hp,Wp,3) u8 out
+ * Ingest: x_lo_out[b] is gcfr_ingest_affine_u8's ingest of photograph photo_index[b] through F[b] (K(F[b]), P0, P1, the clamped
+ * taps, S and the one division, as stated there) -- the bits that entry returns for the gathered photographs
+ * photo_u8[photo_index] -- and the photographs are neither gathered nor copied.
+ * Composite: for every photograph q and every light l the result is the CHAIN of gcfr_fullres_composites_affine_u8's composite over
+ * the faces of q (photo_index[b] = q) in ascending face index b.  The running image starts as the photograph.  Face b applies that
+ * entry's inside test (c0, c1 under I[b]), its carrier with K = K(I[b]), and its p, xl, d, m, r, v and byte through the same device
+ * functions, with the RUNNING byte wherever that entry reads the photograph's: p in the blend v = p + m (r d - p) and p in the
+ * quotient d.  x_lo, rendered and the mask are face b's own.  Outside face b's quad, and where its carried mask m is not positive,
+ * the running byte is kept.  Every step rounds to a byte, as a call of that entry does.
+ *   Consequences.  Where at most one face relights a pixel (inside its quad with m > 0), the byte is
+ *            gcfr_fullres_composites_affine_u8's.  Where two faces relight a pixel, the second face's relighting gain multiplies the
+ *            first face's result, up to the clamps and the intermediate byte: order matters there and nowhere else.  A photograph
+ *            without faces is returned as it is, for every light.  All faces of a photograph share the light index l.
+ *   Anchors, with no tolerance anywhere, overlaps included.
+ *            1. The result equals gcfr_fullres_composites_affine_u8 called once per face with the L lights as its batch -- photo_u8
+ *               the running (L,Hp,Wp,3), I[b] and x_lo[b] repeated L times, rendered[b] passed as (L,1,3,h,w) -- and its output
+ *               taken as the next running image.
+ *            2. With photo_index[b] = b and P = B the bytes are those of ONE call of that entry, and the ingest's bits those of ONE
+ *               call of gcfr_ingest_affine_u8.
+ *            3. With every I the exact inverse of an axis-aligned F at s in {1, 2, 4} and integer x0, y0, every byte is
+ *               gcfr_fullres_composites_group_u8's on the boxes (x0, y0, s w, s h), overlapping boxes included: each link of this
+ *               chain is that entry's link, by the affine entries' anchor and the any-size entries' anchor.
+ * Refusals, each GCFR_ERR_INVALID_ARGUMENT before any launch: a NULL pointer (the maps and `photo_index` included); B < 1, P < 1;
+ * the map rules, for every face; a photo_index outside [0, P); everything gcfr_fullres_composites_u8 refuses of L, mask_batch,
+ * detail_clamp and floor; Hp Wp or h w >= 2^31 or P ceil(Hp Wp / 1024) >= 2^31; an out_u8 whose bytes overlap photo_u8's (the
+ * ingest: x_lo_out == photo_u8).  No gradient, no guided carrying, no perspective maps, no boxes mixed with maps.
+ * Launches: a workgroup owns 1024 consecutive pixels of ONE photograph and walks that photograph's faces in order; a face whose
+ * reachable rows miss the workgroup's rows costs it no 64-bit work.  A launch covers whole photographs, at most 32 of them, with at
+ * most 32 face slots in all (the I maps, K, the reachable rows, face indices and each photograph's slot range by value, about
+ * 2.2 KB: nothing is uploaded, no device scratch, capture-safe).  The running bytes live in out_u8: the first face that relights a
+ * pixel starts from the photograph's bytes, a later one reads back what the same thread stored for that light.  A photograph with
+ * more than 32 faces is launched alone, 32 faces at a time; its continuation launches run on the same stream, start from out_u8
+ * and write only what their faces relight.  A pixel no face relights is copied once per light.  Three dwords per four pixels when
+ * Wp is a multiple of 4 and out_u8 is 4-byte aligned; one element at a time otherwise (same results).  The ingest takes 32 faces
+ * per launch.  Allocates nothing on the device, never synchronises.  Bit-equal to the numpy restatement
+ * (tests/fullres_group_affine_emulation.py).
+ */
+int gcfr_ingest_group_affine_u8(const uint8_t *photo_u8, int32_t P, int32_t Hp, int32_t Wp, const int64_t *F,
+                                const int32_t *photo_index, int32_t B, int32_t h, int32_t w, float *x_lo_out, void *stream);
+int gcfr_fullres_composites_group_affine_u8(const uint8_t *photo_u8, const float *x_lo, const float *rendered, const uint8_t *mask_u8,
+                                            int32_t mask_batch, int32_t P, int32_t B, int32_t L, int32_t Hp, int32_t Wp,
+                                            const int64_t *I, const int32_t *photo_index, int32_t h, int32_t w, float floor,
+                                            float detail_clamp, uint8_t *out_u8, void *stream);
+
 /* ---------------------------------------------------------------------------------------------
  * Environment-map lighting: a lat-long radiance map integrated into the `rgb` (colour x weight per light) of the light-rig stage
  * above (csrc/gcfr_environment.hip).  Every texel belongs to the light direction nearest to it; a light's rgb is the
