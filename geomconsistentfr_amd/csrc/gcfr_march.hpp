@@ -532,6 +532,15 @@ enum { kModeInline = 0, kModeFull = 1, kModeRough = 2 };
 #ifndef GCFR_FRACT_WEIGHTS
 #define GCFR_FRACT_WEIGHTS 1    // 0: every kernel keeps the parent's weights (A/B: tools/build_variant.sh <name> -DGCFR_FRACT_WEIGHTS=0)
 #endif
+// What the compiler adds around the arithmetic of the bounds and termination tests: a value laundered through an
+// empty asm with a read-write constraint is COPIED first when its source stays live behind the asm -- two v_mov_b64, an s_nop and a
+// v_mov_b32 per bounds test.  The same kernels as FRACT (TRIM in march_tile) produce the re-derived value inside the volatile asm from
+// read-only operands instead: nothing to copy and nothing to hoist.  In the main loop's bodies of those kernels the running minimum is one
+// v_min_f32 to which masked lanes hand +inf, and the skip of a sample without an unmasked lane a wave-uniform branch, where the parent
+// has two nested exec-mask regions per sample (MINFORM in eval_sample).
+#ifndef GCFR_VISIT_TRIM
+#define GCFR_VISIT_TRIM 1       // 0: every kernel keeps the parent's launders (A/B: tools/build_variant.sh <name> -DGCFR_VISIT_TRIM=0)
+#endif
 typedef double f64x2 __attribute__((ext_vector_type(2)));
 constexpr int kParkSlots = 4;   // the sample positions of one group: 4 waves x 4 slots x 64 lanes x 16 B = 16 KiB per workgroup
                                 // (six workgroups per CU have 26 KiB each)
@@ -591,6 +600,8 @@ __device__ __forceinline__ bool march_tile(ArgPtr a, const int bl, const int qy,
     // the training march on an untrained network's depth, which runs their untouched rough loop, 0.25 % SLOWER, beyond the parent's
     // spread: profiles/fract_weights_ab.txt): both keep the parent's body, instruction for instruction.
     constexpr bool FRACT = GCFR_FRACT_WEIGHTS && MODE == kModeFull && FUSE_SHADE && !WANT_ARGMIN;
+    // copy-free re-derivation in the bounds and termination tests (see GCFR_VISIT_TRIM): the kernels FRACT selects
+    constexpr bool TRIM = GCFR_VISIT_TRIM && MODE == kModeFull && FUSE_SHADE && !WANT_ARGMIN;
     ParkPlane park = nullptr;  // this wave's plane: [slot][lane]
     if constexpr (PARK)
         park = park_annex(wave);
@@ -850,10 +861,24 @@ __device__ __forceinline__ bool march_tile(ArgPtr a, const int bl, const int qy,
             dyl = finite_ray ? dyf : 0.0f;
             return;
         }
+        if constexpr (TRIM) {
+            // the conversion itself is the volatile asm: dx64 / dy64 are read where they live (v_cvt_f32_f64 rounds to nearest even
+            // under the kernel's mode, as (float) does)
+            asm volatile("v_cvt_f32_f64 %0, %1" : "=v"(dxl) : "v"(dx64));
+            asm volatile("v_cvt_f32_f64 %0, %1" : "=v"(dyl) : "v"(dy64));
+            return;
+        }
         double dx_l = dx64, dy_l = dy64;
         asm volatile("" : "+v"(dx_l), "+v"(dy_l));
         dxl = (float)dx_l;
         dyl = (float)dy_l;
+    };
+    // TRIM: a product the loops must not carry, re-multiplied where it is used -- one v_mul_f32 (an IEEE multiply, contraction is off:
+    // the bits of a * b) inside a volatile asm, so that neither it nor what is computed from it is hoisted, and no operand is copied
+    auto mul_here = [](float p, float q) -> float {
+        float pq;
+        asm volatile("v_mul_f32 %0, %1, %2" : "=v"(pq) : "v"(p), "v"(q));
+        return pq;
     };
     float Kerr = __builtin_inff();  // never skips
     // Early termination (exact).  Once the ray is above max(image depth maximum, 0) by more than the running
@@ -1031,11 +1056,13 @@ __device__ __forceinline__ bool march_tile(ArgPtr a, const int bl, const int qy,
             // (n (cap - zb) + Kerr re-evaluated per test: as a per-lane constant it was one register more than the six-wave
             //  kernel has once the trailing loop is in place; Kerr = +inf where the bound is not valid: gd = -inf)
             float nrm_l = nrm;  // (laundered: or the loop-invariant sub-expression is hoisted back into a register and spilled)
-            asm volatile("" : "+v"(nrm_l));
+            if constexpr (!TRIM)
+                asm volatile("" : "+v"(nrm_l));
+            const float Qz_l = TRIM ? mul_here(nrm, zb) : nrm_l * zb;  // (TRIM: what depends on the asm's product stays here too)
             // (Round 4 measured the trailing loop's per-ray cap -- two horizon-table gathers -- in THIS test too (VERDICT r03 item
             //  5a): bit-identical, and slower: -2.7 % on the bench faces, -3.0 % on the FFHQ fixtures, -3.5 % at B = 128
             //  (profiles/r04_pixels_mainhz_ab.txt).  The main loop rarely terminates, it hands over to the trailing loop.)
-            const float gd = __builtin_fmaf(c1, tn, -(__builtin_fmaf(nrm_l, gz_cap, -(nrm_l * zb)) + Kerr));
+            const float gd = __builtin_fmaf(c1, tn, -(__builtin_fmaf(nrm_l, gz_cap, -Qz_l) + Kerr));
             const float bS = bestS;
             const bool finished = (GCFR_M(11, true, (c1 > 0.0f)) && (gd > 0.0f) && (gd * gd * GCFR_M(7, GCFR_MUT_SLACK_VALUE, 0.998f) > bS) && (bS < safeS)) ||
                                   (lane_last < k0 + DEPTH GCFR_M(26, + 1, ));
@@ -1060,9 +1087,9 @@ __device__ __forceinline__ bool march_tile(ArgPtr a, const int bl, const int qy,
             // (n zb re-multiplied per test from a laundered zb: hoisted out of the loops it is one more live register than the
             //  inference kernel has at six waves -- with the trailing loop in place the allocator spilled Dcap for it)
             float zb_l = zb;
-            if (TRAIL && !WANT_ARGMIN)
+            if (TRAIL && !WANT_ARGMIN && !TRIM)
                 asm volatile("" : "+v"(zb_l));
-            const float Qz = nrm * zb_l;
+            const float Qz = TRIM ? mul_here(nrm, zb) : nrm * zb_l;
             const float Ta = c1 * ta, Tb = c1 * tb;
             const float Tlo = fminf(Ta, Tb), Thi = fmaxf(Ta, Tb);
             // surface band at the sample position s(t) = (x, y) + t d:  z in A0 + t A1 + [c_lo, c_hi], so
@@ -1108,7 +1135,17 @@ __device__ __forceinline__ bool march_tile(ArgPtr a, const int bl, const int qy,
     // - 0.0001 with s + W/2 exact near u = 0 (Sterbenz) and a multiple of ulp(s): |u| >= the distance of the double 0.0001 to that
     // grid, which is >= 2.1e-16 > 2^-54 for |s| >= 2, i.e. for W/2 >= 3 (uy = (H/2 - sy) - 0.0001 likewise).  Smaller images: use_zb.
     // (The floors are handed in by every caller, as in the parent; under FRACT they are unused and, with them, whatever computed them.)
-    auto eval_sample = [&](int k, bool masked, double uxj, double uyj, double fxj, double fyj, const f32x4 &q) {
+    // The running minimum.  Parent's form: bestS = (!masked && S < bestS) ? S : bestS, which the compiler turns into an exec-mask region
+    // per sample (v_cmp, s_and_saveexec, two v_mov, two s_or) inside the exec-mask region of the unmasked lanes.  MINFORM (the main
+    // loop's bodies of the TRIM kernels, see consume()): masked lanes hand +inf to ONE v_min_f32, no region.  The same bits: bestS is
+    // never NaN (it starts at +inf and only ever takes an S that compared below it); S = NaN: the parent's compare is false and keeps
+    // bestS, and v_min_f32 returns its other operand for a quiet NaN -- arithmetic never produces a signalling one --, bestS; S >= kEps4 > 0
+    // otherwise, so no signed zeros meet; S == bestS: either operand is the same value.  The instruction is written out (volatile): as
+    // fminf() it is preceded by a canonicalising v_max_f32, and left to the scheduler the four samples' minima are merged into
+    // v_min3_f32 behind ALL four evaluations, which then overlap and spill (20 B per lane at 16 x 4 / groups of four).
+    auto eval_sample = [&](int k, bool masked, double uxj, double uyj, double fxj, double fyj, const f32x4 &q, auto minform) {
+        constexpr bool MINFORM = decltype(minform)::value;
+        static_assert(!MINFORM || !WANT_ARGMIN, "the argmin chain needs the comparison's outcome");
         double wx0, wx1, wy0, wy1;
         if constexpr (FRACT) {
             bilinear_weights(uxj, GCFR_M(32, wx1, wx0), GCFR_M(32, wx0, wx1));
@@ -1141,7 +1178,12 @@ __device__ __forceinline__ bool march_tile(ArgPtr a, const int bl, const int qy,
             prevk = take ? besti : prevk;
             besti = take ? k : besti;
         }
-        bestS = take ? S : bestS;
+        if constexpr (MINFORM) {
+            const float Sm = GCFR_M(33, S, masked ? __builtin_inff() : S);
+            asm volatile("v_min_f32 %0, %1, %2" : "=v"(bestS) : "v"(Sm), "v"(bestS));
+        } else {
+            bestS = take ? S : bestS;
+        }
     };
 // census: loop: group bookkeeping (ballots, branches)
     bool all_lazy = false;  // (wave-uniform) set by consume(): the group just consumed could have been skipped without its mask
@@ -1230,7 +1272,7 @@ __device__ __forceinline__ bool march_tile(ArgPtr a, const int bl, const int qy,
             // phase 2: bilinear depth, point A, squared distance numerator, running minimum
 #pragma unroll
             for (int j = h0; j < h0 + GCFR_BODY_CHUNK && j < DEPTH; ++j)
-                eval_sample(clampk(k0 + j), (cm[j] == 0) || dead, ux[j], uy[j], fxd[j], fyd[j], qv[j]);
+                eval_sample(clampk(k0 + j), (cm[j] == 0) || dead, ux[j], uy[j], fxd[j], fyd[j], qv[j], std::false_type{});
           }
           } else {
             // (The trailing loop's leave path, LAZY, keeps the plain body: with the pair there the six-wave kernel of even W/2 and
@@ -1280,7 +1322,16 @@ __device__ __forceinline__ bool march_tile(ArgPtr a, const int bl, const int qy,
                 issue(1);
 #pragma unroll
             for (int j = 0; j < DEPTH; ++j) {
-                eval_sample(clampk(k0 + j), ((mflags >> j) & 1u) != 0u, ux[j], uy[j], __builtin_floor(ux[j]), __builtin_floor(uy[j]), qv[j]);
+                if constexpr (TRIM) {
+                    // TRIM: a sample whose lanes are ALL masked is skipped by a wave-uniform branch (what the parent's s_cbranch_execz
+                    // did, and a block boundary per sample: the staging of the gathers holds); in an evaluated sample every lane
+                    // computes S and the masked ones hand +inf to the minimum (MINFORM in eval_sample)
+                    const bool mj = ((mflags >> j) & 1u) != 0u;
+                    if (__builtin_amdgcn_ballot_w64(!mj) != 0ull)
+                        eval_sample(clampk(k0 + j), mj, ux[j], uy[j], __builtin_floor(ux[j]), __builtin_floor(uy[j]), qv[j], std::true_type{});
+                } else {
+                    eval_sample(clampk(k0 + j), ((mflags >> j) & 1u) != 0u, ux[j], uy[j], __builtin_floor(ux[j]), __builtin_floor(uy[j]), qv[j], std::false_type{});
+                }
                 if (j + 2 < DEPTH)
                     issue(j + 2);
                 if (j == (DEPTH >= 3 ? DEPTH - 3 : 0))
@@ -1354,7 +1405,7 @@ __device__ __forceinline__ bool march_tile(ArgPtr a, const int bl, const int qy,
             for (int j = 0; j < CH; ++j) {
                 const bool masked = (mk[j] == 0) || (OWN && (lane_last < 0));
                 any_masked |= masked;
-                eval_sample(clampk(k0 + j), masked, ux[j], uy[j], fxd[j], fyd[j], qv[j]);
+                eval_sample(clampk(k0 + j), masked, ux[j], uy[j], fxd[j], fyd[j], qv[j], std::false_type{});
             }
         }
     } else {
@@ -1452,8 +1503,9 @@ __device__ __forceinline__ bool march_tile(ArgPtr a, const int bl, const int qy,
                     const f32x4 zr4 = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(zr, hz_off + (ir << 4), 0, 0));
                     const float zc = fmaxf(fmaxf(zc4.x, zc4.y), fmaxf(zc4.z, zc4.w)), zr_ = fmaxf(fmaxf(zr4.x, zr4.y), fmaxf(zr4.z, zr4.w));
                     float nrm_l = nrm;  // (laundered, see finish_check)
-                    asm volatile("" : "+v"(nrm_l));
-                    const float Dc = __builtin_fmaf(nrm_l, fminf(zc, zr_), -(nrm_l * zb)) + Kerr;  // (Kerr = inf: never finished)
+                    if constexpr (!TRIM)
+                        asm volatile("" : "+v"(nrm_l));
+                    const float Dc = __builtin_fmaf(nrm_l, fminf(zc, zr_), -(TRIM ? mul_here(nrm, zb) : nrm_l * zb)) + Kerr;  // (Kerr = inf: never finished)
                     const float gd = __builtin_fmaf(c1, tn, -Dc);
                     const bool past = lane_last < k0 + DEPTH GCFR_M(26, + 1, );
                     const bool finished = (GCFR_M(11, true, (c1 > 0.0f)) && (gd > 0.0f) && (gd * gd * GCFR_M(8, GCFR_MUT_SLACK_VALUE, 0.998f) > bestS) && (bestS < safeS)) || past;

@@ -55,6 +55,10 @@
 // 32  fract weights: wx0 = v_fract_f64(-ux), wx1 = v_fract_f64(ux)                  exchanged
 //     (32 changes no margin either: the bilinear weights of the bounds variant of the fused inference grid kernels, DESIGN.md 4.1h.
 //      tests/test_gpu_march_fract_weights.py is the suite it must fail; how many of its cases it fails: profiles/fract_weights_ab.txt.)
+// 33  running minimum as v_min_f32: a masked lane hands +inf to it                   hands its S
+//     (33 changes no margin either: the minimum of the main loop's bodies in the bounds variant of the fused inference grid kernels,
+//      DESIGN.md 4.1i.  tests/test_gpu_march_visit_trim.py is the suite it must fail; how many of its cases it fails:
+//      profiles/visit_trim_ab.txt.)
 //
 // 3 and 5 are the two mutants no END-TO-END test kills (profiles/r05_mutants.md): K1, K2 r and the plane term budget for three different
 // effects -- the 1e-4 position offset times |BCz|, the f32 roundings of the distance's products, the offset times the surface's slope --
@@ -127,3 +131,4 @@
 #define GCFR_MUT_PAIR_30_30 ~, 1
 #define GCFR_MUT_PAIR_31_31 ~, 1
 #define GCFR_MUT_PAIR_32_32 ~, 1
+#define GCFR_MUT_PAIR_33_33 ~, 1
